@@ -8,7 +8,13 @@ BCExtension interpolation, src/stationary_pnp_from_pb.hh:105-282); the Jacobian 
 and R(x0) are the linear system (SURVEY.md §8(d) "Synthetic inputs").
 
 One step = one full residual + Jacobian assembly of the device-resident state (the headline
-`value`, assembled DOFs/s), timed over K steps bracketed by barrier + device sync.  A second
+`value`, assembled DOFs/s), timed over K steps bracketed by barrier + device sync.  A plain run
+stops there: setup, W warmup assemblies, the K timed ones, the result line (`ms_per_step` = one
+timed assembly).  `--dump-outputs DIR` writes what the last timed assembly computed as
+DIR/<name>.npy (dump_outputs; same arguments, same inputs).  Everything below runs with `--full`
+only and adds its keys to the line.
+
+`--full`: a second
 timed region runs K x --bicg-iters BiCGSTAB iterations (ILU0 = multicolour ILU(0) by default) on
 the assembled system and reports BiCGSTAB iterations/s.  Roofline numbers come from HIP events
 recorded on the library's own stream around every assembly launch; `roofline.traffic` is the
@@ -459,12 +465,47 @@ def make_context(mesh, cfg, rank, world, local, dist):
     return ctx, x0, pb_res, time.perf_counter() - t_setup
 
 
-def measure(ctx, mesh, args, prec, dist, world):
-    """Timed regions on one context: warm assembly (the metric), BiCGSTAB, then the event-timed
-    passes (warm, cache-cold) the rooflines are computed from."""
+DUMP_CAP = 1 << 21  # entries per dumped array (16 MiB of float64; three arrays stay under 64 MB)
+DUMP_SEED = 20261019
+
+
+def dump_sample(a):
+    """`a` itself up to DUMP_CAP entries; of a longer array the entries at DUMP_CAP sorted indices
+    drawn once from DUMP_SEED (the same indices for every array of that length)."""
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    if a.size <= DUMP_CAP:
+        return a
+    idx = np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_CAP, replace=False)
+    idx.sort()
+    return a[idx]
+
+
+def dump_outputs(ctx, out_dir, rank, world):
+    """--dump-outputs: what the last timed assembly left in the context, as <name>.npy (float64)
+    under out_dir (`<name>_rank<r>.npy` at N > 1, each rank its owned rows).  The Jacobian is the
+    one a caller reads back with pnp_jacobian_export: `jacobian_values` (the CSR values, external
+    layout, sorted columns) and `jacobian_rowsum` (J times the vector of ones: every entry counts),
+    each sampled by dump_sample.  No call returns the residual of pnp_assemble_state; the solver
+    reads it on the device as its right-hand side, so `residual_norm` is the initial defect one
+    unpreconditioned BiCGSTAB iteration reports for it (run after the export, outside the timed
+    steps)."""
+    os.makedirs(out_dir, exist_ok=True)
+    J = ctx.jacobian_export()
+    res = ctx.bicgstab_iterations(1, P.PREC_NONE)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    for name, a in (("jacobian_values", dump_sample(J.data)),
+                    ("jacobian_rowsum", dump_sample(J @ np.ones(J.shape[1]))),
+                    ("residual_norm", np.array([res["defect0"]]))):
+        np.save(os.path.join(out_dir, f"{name}{sfx}.npy"), a)
+
+
+def measure(ctx, mesh, args, prec, dist, world, dump=None):
+    """Timed regions on one context: warm assembly (the metric) and, with --full, BiCGSTAB, then
+    the event-timed passes (warm, cache-cold) the rooflines are computed from."""
     info = ctx.info()
     ctx.assemble_state(1)  # the solve needs an assembled Jacobian
-    ctx.bicgstab_iterations(max(1, args.warmup), prec)
+    if args.full:
+        ctx.bicgstab_iterations(max(1, args.warmup), prec)
     # the W warmup assemblies right before the timed ones: after a solve the matrix lines are out
     # of the Infinity Cache and it takes two launches to bring the write stream back (rocprofv3
     # trace r2bg: 87, 77, then 48 us)
@@ -475,6 +516,12 @@ def measure(ctx, mesh, args, prec, dist, world):
     ctx.assemble_state(args.steps)
     barrier_sync(dist, world)
     t_asm = time.perf_counter() - t0
+    if dump:
+        dump_outputs(ctx, dump, int(os.environ.get("RANK", "0")), world)
+    if not args.full:  # a plain run: the headline figure only
+        t_asm = max_over_ranks(dist, world, t_asm)
+        return {"info": info, "N_global": 3 * mesh.nv, "N_local": 3 * info["nv_owned"],
+                "t_asm": t_asm, "dofs_per_s": 3 * mesh.nv * args.steps / t_asm}
     # ---- timed region 2: BiCGSTAB --------------------------------------------------------------
     barrier_sync(dist, world)
     t0 = time.perf_counter()
@@ -823,12 +870,53 @@ def primary_mesh(args, world):
     return cfg, tile_mesh(P.Mesh.read_gmsh(cfg.meshfile).refine(args.refine), world)
 
 
+def headline(args, world, mesh, M):
+    """The head of the result line, the same in a plain and a --full run: the metric (assembled
+    DOFs/s over the --steps timed assemblies), `ms_per_step` and the workload."""
+    info = M["info"]
+    if args.scaling == "weak":
+        workload = (f"config 3: stationary 3-ion PNP, test/pore_pnp/pore.msh refined "
+                    f"k={args.refine} x {world} mirrored copies")
+    else:
+        workload = (f"config 5: stationary 3-ion PNP, test/pore_without_dna .geo meshed "
+                    f"natively (scale 0.85), refined k={args.strong_refine}, one mesh "
+                    f"RCB-split over {world} GPU(s)")
+    return {
+        "metric": "assembled DOFs/s + BiCGStab iters/s, 3-species PNP on pore.msh-refined",
+        "value": M["dofs_per_s"],
+        "unit": "assembled DOFs/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": 1e3 * M["t_asm"] / args.steps,
+        "higher_is_better": True,
+        "scaling": args.scaling,
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "reference inputs: test/pore_pnp mesh (refined) + pore.cfg; state = Boltzmann "
+                "initial state from a GPU PB Newton solve (no synthetic vectors)",
+        "config": {"workload": workload,
+                   "dofs": M["N_global"], "dofs_per_gpu": M["N_local"],
+                   "mesh_vertices": mesh.nv, "triangles": mesh.nt,
+                   "parallelism": f"mesh partition (RCB) x{world}",
+                   "preconditioner": args.prec, "colors": info["ncolors"],
+                   "sell_slots": info["nslots"], "blocks": info["nblocks"]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--refine", type=int, default=4)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed assembly steps also run every secondary leg: BiCGSTAB "
+                         "rates, rooflines and stream ceilings, time to solution, BCGS_SSORk, "
+                         "configs 1 / 2 / 4 / 5, the multi-GPU self-check and the CPU baselines "
+                         "(default: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed assembly computed as DIR/<name>.npy "
+                         "(dump_outputs)")
     ap.add_argument("--bicg-iters", type=int, default=20)
     ap.add_argument("--prec", default="ilu0", choices=["none", "jacobi", "ssor", "ilu0", "amg"])
     ap.add_argument("--scaling", default="weak", choices=["weak", "strong"],
@@ -882,17 +970,31 @@ def main():
         dist.init_process_group("gloo")
     prec = P.PREC_BY_NAME[args.prec]
 
-    progress(rank, f"N = {world}: stream ceilings")
-    try:  # a measurement helper: its failure costs the line the measured ceilings, nothing else
-        stream_gbs = measured_stream_gbs(local)
-    except (OSError, RuntimeError) as exc:
-        progress(rank, f"measured_stream_gbs unavailable: {exc}")
-        stream_gbs = None
-    progress(rank, "primary system: mesh, PB Newton, timed assembly and BiCGSTAB")
+    stream_gbs = None
+    if args.full:
+        progress(rank, f"N = {world}: stream ceilings")
+        try:  # a measurement helper: its failure costs the line the measured ceilings, nothing else
+            stream_gbs = measured_stream_gbs(local)
+        except (OSError, RuntimeError) as exc:
+            progress(rank, f"measured_stream_gbs unavailable: {exc}")
+    progress(rank, "primary system: mesh, PB Newton, timed assembly" +
+             (" and BiCGSTAB" if args.full else ""))
     cfg, mesh = primary_mesh(args, world)
     ctx, x0, pb_res, t_setup = make_context(mesh, cfg, rank, world, local, dist)
-    M = measure(ctx, mesh, args, prec, dist, world)
+    M = measure(ctx, mesh, args, prec, dist, world, dump=args.dump_outputs)
     info = M["info"]
+    if not args.full:
+        ctx.close()
+        if rank == 0:
+            line = headline(args, world, mesh, M)
+            line.update(full=False, setup_s=t_setup,
+                        pb_newton={"iterations": pb_res["iterations"],
+                                   "linear_iterations": pb_res["linear_iterations"],
+                                   "converged": pb_res["converged"]})
+            print(json.dumps(line), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
 
     # ---- time to solution (reported beside the metric): PNP Newton from the Boltzmann state ----
     newton = None
@@ -1050,33 +1152,9 @@ def main():
         tm = M["timers"]
         aw, ac, asit = M["asm_warm"], M["asm_cold"], M["asm_situ"]
         traffic = pmc_traffic("k_assemble_ga<0, 1, 3, 9, 6")
-        if args.scaling == "weak":
-            workload = (f"config 3: stationary 3-ion PNP, test/pore_pnp/pore.msh refined "
-                        f"k={args.refine} x {world} mirrored copies")
-        else:
-            workload = (f"config 5: stationary 3-ion PNP, test/pore_without_dna .geo meshed "
-                        f"natively (scale 0.85), refined k={args.strong_refine}, one mesh "
-                        f"RCB-split over {world} GPU(s)")
         line = {
-            "metric": "assembled DOFs/s + BiCGStab iters/s, 3-species PNP on pore.msh-refined",
-            "value": M["dofs_per_s"],
-            "unit": "assembled DOFs/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": 1e3 * M["t_asm"] / args.steps,
-            "higher_is_better": True,
-            "scaling": args.scaling,
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "reference inputs: test/pore_pnp mesh (refined) + pore.cfg; state = Boltzmann "
-                    "initial state from a GPU PB Newton solve (no synthetic vectors)",
-            "config": {"workload": workload,
-                       "dofs": M["N_global"], "dofs_per_gpu": M["N_local"],
-                       "mesh_vertices": mesh.nv, "triangles": mesh.nt,
-                       "parallelism": f"mesh partition (RCB) x{world}",
-                       "preconditioner": args.prec, "colors": info["ncolors"],
-                       "sell_slots": info["nslots"], "blocks": info["nblocks"]},
+            **headline(args, world, mesh, M),
+            "full": True,
             "bicgstab_iters_per_s": M["iters_per_s"],
             "bicgstab_ms_per_iter": 1e3 * M["t_bicg"] / (args.steps * args.bicg_iters),
             "bicgstab_iters_per_s_f64_factors": M["iters_per_s_f64_factors"],

@@ -75,6 +75,20 @@ def test_two_process_gloo_partition_and_halo():
             assert len(ghosts) > 0
 
 
+def test_dump_sample_is_whole_below_the_cap_and_a_fixed_sorted_sample_above():
+    """--dump-outputs: an array up to DUMP_CAP entries is written whole (as float64); a longer one
+    at DUMP_CAP distinct indices in ascending order, the same ones on every call"""
+    B = _bench()
+    small = np.arange(7, dtype=np.float32).reshape(7, 1)
+    s = B.dump_sample(small)
+    assert s.dtype == np.float64 and s.tolist() == list(range(7))
+    big = np.arange(B.DUMP_CAP + 1000, dtype=np.float64)  # value = index
+    a, b = B.dump_sample(big), B.dump_sample(big.copy())
+    assert a.shape == (B.DUMP_CAP,) and np.array_equal(a, b)
+    assert np.all(np.diff(a) > 0) and a[0] >= 0 and a[-1] < big.size
+    assert 3 * 8 * B.DUMP_CAP <= 64e6  # the three arrays of a dump
+
+
 def test_guarded_leg_records_an_error_and_passes_results_through():
     """a secondary bench leg that raises on every rank costs the line that leg only"""
     import pnp_amd as P

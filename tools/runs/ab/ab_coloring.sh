@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/$1; mkdir -p "$OUT"; : > "$OUT/ab_coloring.log"
 for prec in ${PRECS:-ilu0 ssor}; do
   for c in sl greedy; do
-    PNP_COLORING=$c timeout -k 10 300 python bench.py --no-cpu --steps 10 --prec $prec > "$OUT/col_${prec}_$c.log" 2>&1 || exit $?
+    PNP_COLORING=$c timeout -k 10 300 python bench.py --full --no-cpu --steps 10 --prec $prec > "$OUT/col_${prec}_$c.log" 2>&1 || exit $?
     python - "$OUT/col_${prec}_$c.log" $prec $c >> "$OUT/ab_coloring.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

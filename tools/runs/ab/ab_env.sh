@@ -9,7 +9,7 @@ PRECS=${*:-ilu0}
 mkdir -p "$OUT"; LOG="$OUT/ab_${VAR}.log"; : > "$LOG"
 for prec in $PRECS; do
   for v in $VALS; do
-    env "$VAR=$v" timeout -k 10 300 python bench.py --no-cpu --steps 10 --prec "$prec" > "$OUT/ab_${VAR}_${prec}_$v.log" 2>&1 || exit $?
+    env "$VAR=$v" timeout -k 10 300 python bench.py --full --no-cpu --steps 10 --prec "$prec" > "$OUT/ab_${VAR}_${prec}_$v.log" 2>&1 || exit $?
     python - "$OUT/ab_${VAR}_${prec}_$v.log" "$prec" "$VAR=$v" >> "$LOG" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

@@ -8,7 +8,7 @@ OUT=$1; A=$2; B=$3; shift 3
 for round in 1 2; do
   for setting in "$A" "$B"; do
     echo "== $setting round $round" >> "$OUT"
-    env $setting timeout -k 10 300 python bench.py --no-cpu --no-strong --no-amg "$@" > /tmp/ab_line.json 2>/tmp/ab_err.log
+    env $setting timeout -k 10 300 python bench.py --full --no-cpu --no-strong --no-amg "$@" > /tmp/ab_line.json 2>/tmp/ab_err.log
     rc=$?
     if [ $rc -ne 0 ]; then echo "rc=$rc" >> "$OUT"; tail -5 /tmp/ab_err.log >> "$OUT"; exit $rc; fi
     python - >> "$OUT" <<'PY'

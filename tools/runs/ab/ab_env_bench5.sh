@@ -9,7 +9,7 @@ OUT=$1; A=$2; B=$3
 for round in 1 2; do
   for setting in "$A" "$B"; do
     echo "== $setting round $round" >> "$OUT"
-    env $setting timeout -k 10 400 python bench.py --no-cpu --no-amg --no-parity > /tmp/ab5_line.json 2>/tmp/ab5_err.log
+    env $setting timeout -k 10 400 python bench.py --full --no-cpu --no-amg --no-parity > /tmp/ab5_line.json 2>/tmp/ab5_err.log
     rc=$?
     if [ $rc -ne 0 ]; then echo "rc=$rc" >> "$OUT"; tail -5 /tmp/ab5_err.log >> "$OUT"; exit $rc; fi
     python - >> "$OUT" <<'PY'

@@ -4,7 +4,7 @@ set -u
 OUT=gpurun_out/$1; mkdir -p "$OUT"; : > "$OUT/ab_lib_bench.log"
 for i in 1 2; do
   for v in new base; do
-    PNP_AMD_LIB=dune-pnp_amd/ab/lib_$v.so timeout -k 10 300 python bench.py --no-cpu --steps 10 > "$OUT/ab_lb_$v.log" 2>&1 || exit $?
+    PNP_AMD_LIB=dune-pnp_amd/ab/lib_$v.so timeout -k 10 300 python bench.py --full --no-cpu --steps 10 > "$OUT/ab_lb_$v.log" 2>&1 || exit $?
     python - "$OUT/ab_lb_$v.log" "$v" >> "$OUT/ab_lib_bench.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

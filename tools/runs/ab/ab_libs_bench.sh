@@ -7,7 +7,7 @@ OUT=gpurun_out/$1; shift; mkdir -p "$OUT"; : > "$OUT/ab.log"
 for i in 1 2; do
   for lib in "$@"; do
     if [ "$lib" = "-" ]; then libenv=""; else libenv="PNP_AMD_LIB=dune-pnp_amd/ab/lib_$lib.so"; fi
-    env $libenv timeout -k 10 400 python bench.py --no-cpu --no-amg --no-parity > /tmp/abl_line.json 2>/tmp/abl_err.log
+    env $libenv timeout -k 10 400 python bench.py --full --no-cpu --no-amg --no-parity > /tmp/abl_line.json 2>/tmp/abl_err.log
     rc=$?
     if [ $rc -ne 0 ]; then echo "$lib rc=$rc" >> "$OUT/ab.log"; tail -5 /tmp/abl_err.log >> "$OUT/ab.log"; exit $rc; fi
     python - "$lib" >> "$OUT/ab.log" <<'PY'

@@ -3,7 +3,7 @@
 set -u
 OUT=gpurun_out/$1; shift; mkdir -p "$OUT"; : > "$OUT/ab_sweep.log"
 run() {  # prec cfg
-  PNP_SWEEP=$2 timeout -k 10 200 python bench.py --no-cpu --no-solve --steps 10 --prec $1 > "$OUT/sw_$1_$2.log" 2>&1
+  PNP_SWEEP=$2 timeout -k 10 200 python bench.py --full --no-cpu --no-solve --steps 10 --prec $1 > "$OUT/sw_$1_$2.log" 2>&1
   local rc=$?; [ $rc -ne 0 ] && { echo "rc=$rc prec=$1 cfg=$2" >> "$OUT/ab_sweep.log"; return $rc; }
   python - "$OUT/sw_$1_$2.log" $1 $2 >> "$OUT/ab_sweep.log" <<'PY'
 import json, sys

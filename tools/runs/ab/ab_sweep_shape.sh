@@ -6,7 +6,7 @@ set -u
 OUT=gpurun_out/$1; shift; mkdir -p "$OUT"; : > "$OUT/ab_sweep.log"
 for round in 1 2; do
   for sh in "$@"; do
-    PNP_SWEEP=$sh timeout -k 10 300 python bench.py --no-cpu --no-strong --no-amg --steps 10 > "$OUT/b_$sh.json" 2>&1 || exit $?
+    PNP_SWEEP=$sh timeout -k 10 300 python bench.py --full --no-cpu --no-strong --no-amg --steps 10 > "$OUT/b_$sh.json" 2>&1 || exit $?
     python - "$OUT/b_$sh.json" "$sh" >> "$OUT/ab_sweep.log" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])

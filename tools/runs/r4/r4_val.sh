@@ -7,4 +7,4 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 600 --timeout-me
 [ $rc -gt 1 ] && exit $rc
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 900 python -u bench.py > $O/bench.log 2>&1; rc=$?; echo "bench rc=$rc"
+timeout -k 10 900 python -u bench.py --full > $O/bench.log 2>&1; rc=$?; echo "bench rc=$rc"

@@ -11,4 +11,4 @@ timeout -k 10 900 python -u -m pytest tests/test_gpu_ssor_chain.py -x -q --timeo
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 400 python -u tools/newton_ssork.py 4 > $O/newton_ssork.log 2>&1; rc=$?; echo "newton rc=$rc"
 [ $rc -ne 0 ] && exit $rc
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1; echo "bench rc=$?"
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"

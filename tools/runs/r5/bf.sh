@@ -10,7 +10,7 @@ timeout -k 10 300 python -u tools/ab_ilu_bf16.py 3 > $O/ab.log 2>&1; rc=$?; echo
 fatal $rc && exit $rc
 PNP_ILU_F32=2 timeout -k 10 400 python -u tools/tts_spread.py 6 > $O/spread_bf16.log 2>&1; rc=$?; echo "spread rc=$rc: $(tail -1 $O/spread_bf16.log)"
 fatal $rc && exit $rc
-PNP_ILU_F32=2 timeout -k 10 600 python -u bench.py --no-cpu > $O/bench_bf16.log 2>&1; rc=$?; echo "bench rc=$rc"
+PNP_ILU_F32=2 timeout -k 10 600 python -u bench.py --full --no-cpu > $O/bench_bf16.log 2>&1; rc=$?; echo "bench rc=$rc"
 fatal $rc && exit $rc
 PNP_ILU_F32=2 timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 300 --timeout-method thread -rf > $O/tests_bf16.log 2>&1; rc=$?; echo "tests rc=$rc"; tail -8 $O/tests_bf16.log
 exit 0

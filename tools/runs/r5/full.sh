@@ -14,10 +14,10 @@ fatal $rc && exit $rc
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; rc=$?; echo "smoke rc=$rc"; tail -2 $O/smoke.log
 fatal $rc && exit $rc
 fi
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1; rc=$?; echo "bench rc=$rc"; tail -c 400 $O/bench.log
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1; rc=$?; echo "bench rc=$rc"; tail -c 400 $O/bench.log
 fatal $rc && exit $rc
 [ "${NOPROF:-0}" = 1 ] && exit 0
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --no-cpu --no-per-config > $O/prof.log 2>&1; rc=$?; echo "prof rc=$rc"
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 bench.py --full --no-cpu --no-per-config > $O/prof.log 2>&1; rc=$?; echo "prof rc=$rc"
 fatal $rc && exit $rc
 python tools/asm_regimes.py $O/prof/run_kernel_trace.csv 353561080 $O/asm_regimes_config3.json "k_assemble_ga<0, 1, 3, 9, 6" 738048 > $O/asm_regimes.log 2>&1
 python tools/nat_split.py $O/prof/run_kernel_trace.csv > $O/nat_split.log 2>&1

@@ -20,7 +20,7 @@ fatal $rc && exit $rc
 timeout -k 10 400 python -u -m pytest -x -q --timeout 350 --timeout-method thread tests/test_gpu_asm_lds.py > $O/tests_asm.log 2>&1; rc=$?; echo "asm tests rc=$rc"; tail -2 $O/tests_asm.log
 fatal $rc && exit $rc
 for i in 1 2; do for j in 1 0; do
-  PNP_ASM_JIT=$j timeout -k 10 300 python -u bench.py --no-cpu --no-solve --no-strong --no-ssork --no-per-config --no-amg --steps 20 > $O/asm_jit${j}_$i.log 2>&1; rc=$?; echo "asm jit=$j rc=$rc"
+  PNP_ASM_JIT=$j timeout -k 10 300 python -u bench.py --full --no-cpu --no-solve --no-strong --no-ssork --no-per-config --no-amg --steps 20 > $O/asm_jit${j}_$i.log 2>&1; rc=$?; echo "asm jit=$j rc=$rc"
   fatal $rc && exit $rc
   python - $O/asm_jit${j}_$i.log <<'PY'
 import json, sys

@@ -4,7 +4,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/../../..}"
 O=gpurun_out/r5w; mkdir -p $O
-timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --transport host --steps 3 --warmup 1 --bicg-iters 5 --no-cpu > $O/bench2.log 2>&1; rc=$?; echo "bench N=2 host rc=$rc"
+timeout -k 10 900 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --full --gpus 2 --transport host --steps 3 --warmup 1 --bicg-iters 5 --no-cpu > $O/bench2.log 2>&1; rc=$?; echo "bench N=2 host rc=$rc"
 python3 - <<'PY'
 import json
 d=[json.loads(l) for l in open("gpurun_out/r5w/bench2.log") if l.startswith("{")]

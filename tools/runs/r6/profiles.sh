@@ -5,7 +5,7 @@ set -u
 O=gpurun_out/$1; mkdir -p "$O"
 export TMPDIR=/tmp
 fatal() { case $1 in 124|134|137|139) return 0;; esac; [ "$1" -gt 128 ] && return 0; return 1; }
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_trace" -o run -- python3 bench.py --no-cpu --no-per-config > "$O/bench_traced.json" 2> "$O/bench_traced.err"; rc=$?; echo "bench trace=$rc"; gzip -f "$O"/bench_trace/*kernel_trace.csv; fatal $rc && exit 1
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bench_trace" -o run -- python3 bench.py --full --no-cpu --no-per-config > "$O/bench_traced.json" 2> "$O/bench_traced.err"; rc=$?; echo "bench trace=$rc"; gzip -f "$O"/bench_trace/*kernel_trace.csv; fatal $rc && exit 1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/bicg" -o run -- python3 tools/prof_bicg.py 20 3,5 > "$O/prof_bicg.log" 2>&1; rc=$?; echo "bicg trace=$rc"; fatal $rc && exit 1
 bash tools/gpu_run.sh "$1" pmcf pmcw; rc=$?; echo "pmc=$rc"; fatal $rc && exit 1
 F=$(ls "$O"/pmc_fetch/*counter_collection.csv | head -1); W=$(ls "$O"/pmc_write/*counter_collection.csv | head -1)
