@@ -22,6 +22,7 @@
 
 #include "../../include/pnp_capi.h"
 #include "amg.h"
+#include "gmres_small.h"
 #include "kernels.h"
 #include "mesh.h"
 #include "pk.h"
@@ -347,6 +348,12 @@ struct pnp_ctx {
   std::vector<double> newton_defects; // and the defect after each step
   DBuf<pnp::Scalars> S;
   pnp::Scalars *hS = nullptr;  // pinned host mirror
+  // restarted GMRES / FGMRES (gmres()): basis V, preconditioned basis Z (flexible only), the
+  // orthogonalisation's partials, the device state block and history; allocated on first use
+  int gm_restart = 30;  // PNP_OPT_GMRES_RESTART
+  DBuf<double> gm_V, gm_Z, gm_part, gm_hist;
+  DBuf<pnp::GmresState> gm_S;
+  std::vector<double> gm_history;  // the last GMRES / FGMRES solve's (pnp_solve_history)
 
   // timers / debugging
   bool timing = false;
@@ -2304,6 +2311,192 @@ struct pnp_ctx {
     return PNP_OK;
   }
 
+  // Restarted GMRES(m) (flexible: the preconditioned basis Z is kept, x = x0 + Z y) on
+  // J zout = bdev (owned rows), zero start, right-preconditioned: the monitored norm is the true
+  // residual's.  DESIGN.md 4.8.  The state (Hessenberg matrix, rotations, history, flags) lives on
+  // the device (gmres_small.h); the host enqueues Arnoldi steps and reads the state's header only
+  // at the check_every poll.  A cycle ends on the device (phase 1: the step kernels idle) when the
+  // estimate meets the test, at the restart length or at maxit; the host enqueues the cycle end
+  // (x update, r = b - A x, the true norm, the next cycle's V_0) where it knows a cycle is over:
+  // after m steps, or after a poll that shows phase 1.  Until then the preconditioner and the
+  // SpMV of the enqueued steps run on vectors nobody reads.
+  int gmres_alloc(bool flexible) {
+    const size_t ld = (size_t(nf) * size_t(dl.n_local) + 1) & ~size_t(1);
+    const int m = gm_restart;
+    hipError_t e = hipSuccess;
+    if (gm_V.n != ld * size_t(m + 1)) e = gm_V.alloc(ld * size_t(m + 1));
+    if (e == hipSuccess && flexible && gm_Z.n != ld * size_t(m)) e = gm_Z.alloc(ld * size_t(m));
+    const size_t nps = size_t(pnp::gmres_nparts(nown()));
+    if (e == hipSuccess && gm_part.n != nps * (pnp::kGmMaxRestart + 2))
+      e = gm_part.alloc(nps * (pnp::kGmMaxRestart + 2));
+    if (e == hipSuccess && !gm_S.p) e = gm_S.alloc(1);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "gmres basis");
+  }
+  void gmres_free() {
+    gm_V.release();
+    gm_Z.release();
+    gm_part.release();
+  }
+
+  int gmres(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res,
+            bool flexible) {
+    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
+    if (o.maxit < 0) return fail(PNP_E_ARG, "maxit must not be negative");
+    static_assert(offsetof(pnp::GmresState, red1) <= sizeof(pnp::Scalars), "poll staging");
+    const size_t hdr = offsetof(pnp::GmresState, red1);
+    double t_start = now_s();
+    const long long n = nown();
+    const int m = gm_restart, prec = o.prec;
+    if (prec == PNP_PREC_NONE) flexible = false;  // Z = V
+    int rc;
+    if ((rc = gmres_alloc(flexible))) return rc;
+    const long long ld = (long long)((size_t(nf) * size_t(dl.n_local) + 1) & ~size_t(1));
+    const int nps = pnp::gmres_nparts(n);
+    hipError_t e = hipSuccess;
+    // the history keeps the first kGmHistCap steps: a "no limit" maxit must not size a buffer
+    const int hcap = std::min(o.maxit, pnp::kGmHistCap);
+    if (gm_hist.n < size_t(hcap) + 2) e = gm_hist.alloc(size_t(hcap) + 2);
+    if (e != hipSuccess) return hipfail(e, "gmres history");
+    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
+    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
+    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
+    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
+    pnp::GmresState *St = gm_S.p;
+    pnp::GmresState *hp = reinterpret_cast<pnp::GmresState *>(hS);  // header only
+    {
+      pnp::GmresState *init = reinterpret_cast<pnp::GmresState *>(hS + 2);
+      std::memset(init, 0, hdr);
+      init->reduction = o.reduction;
+      init->m = m;
+      init->maxit = o.maxit;
+      init->phase = 1;  // the start is a cycle end with no columns
+      init->hcap = hcap;
+      e = hipMemcpyAsync(St, init, hdr, hipMemcpyHostToDevice, stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(rs.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return hipfail(e, "gmres init");
+    auto V = [&](int i) { return gm_V.p + size_t(i) * size_t(ld); };
+    auto Z = [&](int i) { return gm_Z.p + size_t(i) * size_t(ld); };
+    auto allred = [&](double *d, int k) -> int {
+      if (!dist) return PNP_OK;
+      hipEvent_t t0 = tb(T_ALLRED);
+      int r2 = allreduce_dev(d, k);
+      if (r2) return r2;
+      te(T_ALLRED, t0);
+      return PNP_OK;
+    };
+    // ||rs||, the true norm's test, V_0 of the next cycle
+    auto close_cycle = [&](int first) -> int {
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_gmres_norm2(St, rs.p, n, gm_part.p, nps, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "gmres norm");
+      te(T_BLAS, t0);
+      int r2 = allred(St->red3, 1);
+      if (r2) return r2;
+      t0 = tb(T_BLAS);
+      e2 = pnp::launch_gmres_restart(St, gm_hist.p, first, gm_V.p, ld, n, rs.p, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "gmres restart");
+      te(T_BLAS, t0);
+      return PNP_OK;
+    };
+    auto cycle_end = [&]() -> int {
+      int nsp = 0, r2;
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_gmres_backsub(St, stream);
+      if (e2 == hipSuccess) {
+        if (flexible)  // x += Z y
+          e2 = pnp::launch_gmres_combine(St, gm_Z.p, ld, n, zout, 1, stream);
+        else if (prec == PNP_PREC_NONE)  // x += V y
+          e2 = pnp::launch_gmres_combine(St, gm_V.p, ld, n, zout, 1, stream);
+        else  // t = V y
+          e2 = pnp::launch_gmres_combine(St, gm_V.p, ld, n, t.p, 0, stream);
+      }
+      if (e2 != hipSuccess) return hipfail(e2, "gmres update");
+      te(T_BLAS, t0);
+      if (!flexible && prec != PNP_PREC_NONE) {  // x += M^-1 t
+        if ((r2 = precond(prec, t.p, y.p))) return r2;
+        t0 = tb(T_BLAS);
+        if ((e2 = pnp::launch_gmres_xpy(St, zout, y.p, n, stream)) != hipSuccess)
+          return hipfail(e2, "gmres update");
+        te(T_BLAS, t0);
+      }
+      if ((r2 = halo_spmv(zout, rs.p, 3, bdev, nullptr, &nsp))) return r2;  // r = b - A x
+      return close_cycle(0);
+    };
+    // one Arnoldi step with the host's column index hj (the device's own j while it steps)
+    auto step = [&](int hj) -> int {
+      int nsp = 0, r2;
+      double *in = V(hj);
+      if (prec != PNP_PREC_NONE) {
+        in = flexible ? Z(hj) : y.p;
+        if ((r2 = precond(prec, V(hj), in))) return r2;
+      }
+      if ((r2 = halo_spmv(in, V(hj + 1), 0, nullptr, nullptr, &nsp))) return r2;
+      double *red[3] = {St->red1, St->red2, St->red3};
+      const int cnt[3] = {hj + 2, hj + 1, 1};
+      for (int pass = 0; pass < 3; pass++) {
+        hipEvent_t t0 = tb(T_BLAS);
+        hipError_t e2 = pnp::launch_gmres_orth(pass, St, gm_V.p, ld, n, gm_part.p, nps, hj, stream);
+        if (e2 != hipSuccess) return hipfail(e2, "gmres orthogonalisation");
+        te(T_BLAS, t0);
+        if ((r2 = allred(red[pass], cnt[pass]))) return r2;
+      }
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_gmres_hess(St, gm_hist.p, gm_V.p, ld, n, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "gmres hessenberg");
+      te(T_BLAS, t0);
+      return PNP_OK;
+    };
+    auto poll = [&]() -> int {
+      hipError_t e2 = hipMemcpyAsync(hp, St, hdr, hipMemcpyDeviceToHost, stream);
+      if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
+      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "gmres poll");
+    };
+    if ((rc = close_cycle(1))) return rc;
+    const int check = o.check_every > 0 ? o.check_every : 8;
+    int hj = 0, it_known = 0;
+    if ((rc = poll())) return rc;
+    while (!hp->done) {
+      // steps until the next poll: never past the restart length or maxit, and one at a time
+      // once the estimate is within a decade of the target (a step enqueued after the device has
+      // ended the cycle costs a whole preconditioner application and an SpMV for nothing)
+      const bool near = hp->norm < 10.0 * o.reduction * hp->norm0;
+      const int ns = std::max(1, std::min({near ? 1 : check, m - hj, o.maxit - it_known}));
+      for (int q = 0; q < ns; q++, hj++)
+        if ((rc = step(hj))) return rc;
+      if (hj == m) {  // the device's cycle is over at the latest now
+        if ((rc = cycle_end())) return rc;
+        hj = 0;
+      }
+      if ((rc = poll())) return rc;
+      if (hp->done) break;
+      if (hp->phase == 1) {  // ended early on the device: estimate met, maxit or breakdown
+        if ((rc = cycle_end())) return rc;
+        hj = 0;
+        if ((rc = poll())) return rc;
+      }
+      it_known = hp->it;
+    }
+    if (prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
+    if (prec == PNP_PREC_ILU0 && (rc = ilu_flow_check())) return rc;
+    gm_history.assign(size_t(std::min(hp->it, hcap)) + 1, 0.0);
+    e = hipMemcpyAsync(gm_history.data(), gm_hist.p, sizeof(double) * gm_history.size(),
+                       hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "gmres history");
+    res.converged = hp->done == 1 ? 1 : 0;
+    res.breakdown = hp->breakdown;
+    res.iterations = hp->it;
+    res.it_half = hp->it;
+    res.defect0 = hp->norm0;
+    res.defect = hp->norm;
+    res.reduction = hp->norm0 > 0 ? hp->norm / hp->norm0 : 0.0;
+    res.elapsed = now_s() - t_start;
+    return PNP_OK;
+  }
+
   // ---- reference-order mode (PNP_OPT_SEQ_ORDER) ------------------------------------------------
   // The reference's single-rank arithmetic in its order (seq_order.hip): element-order assembly
   // into the CSR view, ISTL's sequential mv / dot / updates, the scalar recurrences here in double.
@@ -2646,12 +2839,16 @@ struct pnp_ctx {
   int krylov(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res) {
     int rc;
     after_solve = true;
+    gm_history.clear();
     if (o.method == PNP_METHOD_CG) {
       amg_symmetric = true;
       rc = cg(bdev, zout, o, res);
     } else if (o.method == PNP_METHOD_BICGSTAB) {
       amg_symmetric = false;
       rc = bicgstab(bdev, zout, o, res, 0);
+    } else if (o.method == PNP_METHOD_GMRES || o.method == PNP_METHOD_FGMRES) {
+      amg_symmetric = false;
+      rc = gmres(bdev, zout, o, res, o.method == PNP_METHOD_FGMRES);
     } else {
       return fail(PNP_E_ARG, "unknown solver method");
     }
@@ -3801,6 +3998,7 @@ extern "C" int pnp_jacobian_apply(pnp_ctx *c, const double *x, const double *z, 
 static int seq_solve_abi(pnp_ctx *c, const double *rhs, double *z, const pnp_solve_opts &o,
                          pnp_solve_result &res, bool dev) {
   int rc;
+  c->gm_history.clear();
   if ((rc = c->seq_build())) return rc;
   const size_t n = c->nseq();
   double *sb = c->sq(pnp_ctx::SQ_B), *sz = c->sq(pnp_ctx::SQ_Z);
@@ -3827,6 +4025,13 @@ extern "C" int pnp_linear_solve_ex(pnp_ctx *c, const double *rhs, double *z,
   if ((rc = c->krylov(c->b.p, c->z.p, *o, *res))) return rc;
   if ((rc = c->download_ext(c->z.p, c->nf, z, dev))) return rc;
   return res->breakdown ? PNP_E_BREAKDOWN : PNP_OK;
+}
+
+extern "C" int pnp_solve_history(pnp_ctx *c, double *defects, int32_t cap, int32_t *n) {
+  if (!c || !n || cap < 0 || (cap > 0 && !defects)) return PNP_E_ARG;
+  *n = int32_t(c->gm_history.size());
+  for (int32_t k = 0; k < cap && k < *n; k++) defects[k] = c->gm_history[size_t(k)];
+  return PNP_OK;
 }
 
 extern "C" int pnp_jacobian_csr_device(pnp_ctx *c, pnp_csr_view *out) {
@@ -3922,6 +4127,16 @@ extern "C" int pnp_set_option(pnp_ctx *c, int32_t option, int64_t value) {
     c->ilu_retry = int(value);
     return PNP_OK;
   }
+  if (option == PNP_OPT_GMRES_RESTART) {
+    if (!pnp::gm_restart_valid(value))
+      return c->fail(PNP_E_ARG, "PNP_OPT_GMRES_RESTART takes 2 .. 128");
+    if (c->gm_restart != int(value)) {
+      hipSetDevice(c->device);
+      c->gmres_free();
+      c->gm_restart = int(value);
+    }
+    return PNP_OK;
+  }
   if (option == PNP_OPT_BICG_TWORED) {
     if (value < -1 || value > 1) return c->fail(PNP_E_ARG, "PNP_OPT_BICG_TWORED takes -1, 0 or 1");
     c->twored_opt = int(value);
@@ -3992,6 +4207,10 @@ extern "C" int pnp_get_option(pnp_ctx *c, int32_t option, int64_t *value) {
   }
   if (option == PNP_OPT_JAC_FD) {
     *value = c->fd_opt;
+    return PNP_OK;
+  }
+  if (option == PNP_OPT_GMRES_RESTART) {
+    *value = c->gm_restart;
     return PNP_OK;
   }
   if (option == PNP_OPT_BICG_TWORED) {

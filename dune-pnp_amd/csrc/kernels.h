@@ -565,6 +565,33 @@ hipError_t launch_seq_axpy(int n, double a, double *x, const double *y, hipStrea
 hipError_t launch_seq_aymx(int n, double a, double *x, const double *y, hipStream_t s);
 hipError_t launch_seq_cg_p(int n, double beta, double *p, const double *q, hipStream_t s);
 
+// ---- restarted GMRES / FGMRES (gmres.hip; the state block and the small dense part in
+// gmres_small.h) ------------------------------------------------------------------------------
+// V: basis, vector i at V + i * ld (ld even, >= n); n = n_owned * nf entries are orthogonalised.
+// part: kGmMaxRestart + 2 rows of nps partials; gmres_nparts(n) <= nps workgroups write them.
+// Every launch reads j / phase / done from S and does nothing outside its phase.
+struct GmresState;
+int gmres_nparts(long long n);
+// one pass of the twice-applied classical Gram-Schmidt on w = V_{j+1} and its reduction:
+// mode 0: S->red1 = <V_i, w> (i <= j), <w, w>; mode 1: w -= sum red1[i] V_i, S->red2 = <V_i, w>;
+// mode 2: w -= sum red2[i] V_i, S->red3[0] = <w, w>.  jmax: the host's bound on j (grid size)
+hipError_t launch_gmres_orth(int mode, GmresState *S, double *V, long long ld, long long n,
+                             double *part, int nps, int jmax, hipStream_t s);
+// Hessenberg column + Givens + stop test (one thread), then V_{j+1} *= 1 / h_{j+1,j}
+hipError_t launch_gmres_hess(GmresState *S, double *hist, double *V, long long ld, long long n,
+                             hipStream_t s);
+// cycle end: R y = g; out = (add ? out : 0) + sum_{i<j} y_i B_i; x += d; S->red3[0] = ||a||^2;
+// then the true norm's stop test and, if the solve goes on, V_0 = r / ||r||
+hipError_t launch_gmres_backsub(GmresState *S, hipStream_t s);
+hipError_t launch_gmres_combine(const GmresState *S, const double *B, long long ld, long long n,
+                                double *out, int add, hipStream_t s);
+hipError_t launch_gmres_xpy(const GmresState *S, double *x, const double *d, long long n,
+                            hipStream_t s);
+hipError_t launch_gmres_norm2(GmresState *S, const double *a, long long n, double *part, int nps,
+                              hipStream_t s);
+hipError_t launch_gmres_restart(GmresState *S, double *hist, int first, double *V, long long ld,
+                                long long n, const double *r, hipStream_t s);
+
 // read n doubles of buf (cache scrub before a cache-cold timing; sink is never written)
 hipError_t launch_scrub(const double *buf, long long n, double *sink, hipStream_t s);
 

@@ -9,6 +9,8 @@
 // usage: pnp_main <config.cfg> [--refine k] [--mode stationary|instationary|md|pb] [--steps n]
 //                 [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec ...] [--amg-smoother s]
 //                 [--device d] [--out prefix]
+//                 [--method bicgstab|cg|gmres|fgmres] [--restart m]  (the PNP phases' Krylov method,
+//                                 default bicgstab; m: the GMRES restart length, 2 .. 128, default 30)
 //                 [--md-reduction r]
 //                 [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]
 //                 (bcgs_ssork, the reference's default: ISTL SeqSSOR in the lexicographic order,
@@ -55,6 +57,7 @@ static void usage() {
       "usage: pnp_main <config.cfg> [--refine k] [--mesh-scale s] [--mode stationary|instationary|md|pb]\n"
       "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec p]\n"
       "                [--device d]\n"
+      "                [--method bicgstab|cg|gmres|fgmres] [--restart m]\n"
       "                [--amg-smoother ssor|ilu0|jacobi]\n"
       "                [--out prefix] [--md-reduction r]\n"
       "                [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]\n"
@@ -195,6 +198,8 @@ int main(int argc, char **argv) {
   std::vector<int> dump_steps;  // instationary: write the state after these steps (1-based)
   // md mode: PbLS, the compile-time LINEARSOLVER of src/instationary_pnp_from_pb_md.hh:20-32,188-211
   std::string linsolver = "bcgs_ssork";
+  std::string method = "bicgstab";  // the Krylov method of the PNP phases (stationary / instationary)
+  int restart = 0;                  // > 0: PNP_OPT_GMRES_RESTART
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -214,6 +219,8 @@ int main(int argc, char **argv) {
     else if (a == "--linear-solver") linsolver = next();
     else if (a == "--abs-limit") abs_limit = std::atof(next().c_str());
     else if (a == "--degree") degree = std::atoi(next().c_str());
+    else if (a == "--method") method = next();
+    else if (a == "--restart") restart = std::atoi(next().c_str());
     else if (a == "--reference-solvers") {
       pb_prec = "ssor_natural";
       prec = "none";
@@ -303,8 +310,15 @@ int main(int argc, char **argv) {
     // ---- PNP initial state (interpolate(BCExtension), :282) --------------------------------
     V u(3 * size_t(nv));
     pnp_gpu::check(pnp_initial_state(ctx.get(), pbu.data(), u.data()), ctx.get());
+    int pnp_method = PNP_METHOD_BICGSTAB;
+    if (method == "cg") pnp_method = PNP_METHOD_CG;
+    else if (method == "gmres") pnp_method = PNP_METHOD_GMRES;
+    else if (method == "fgmres") pnp_method = PNP_METHOD_FGMRES;
+    else if (method != "bicgstab") throw pnp_gpu::Error(PNP_E_ARG, "unknown --method " + method);
+    if (restart > 0)
+      pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_GMRES_RESTART, restart), ctx.get());
     pnp_gpu::BiCGStabBackend<V> ls(ctx, s.cfg.linear_solver_iterations, prec_of(prec),
-                                   rank == 0 ? s.cfg.verbosity : 0);
+                                   rank == 0 ? s.cfg.verbosity : 0, pnp_method);
     if (prec == "amg") amg_for("ilu0");
     auto configure = [&](pnp_gpu::Newton<V> &nw) {
       nw.setReduction(s.cfg.newton_reduction);

@@ -32,9 +32,10 @@ OK, E_ARG, E_HIP, E_RCCL, E_BREAKDOWN, E_NOT_CONVERGED, E_IO, E_MESH, E_STATE = 
     0, -1, -2, -3, -4, -5, -6, -7, -8
 OP_PNP, OP_PNP_IMPLICIT_EULER, OP_PB, OP_DIFF, OP_DIFF_IMPLICIT_EULER, OP_POISSON = range(6)
 PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL = range(6)
-METHOD_BICGSTAB, METHOD_CG = 0, 1
+METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES = 0, 1, 2, 3
 (OPT_ILU_F32, OPT_ILU_FUSED_FACTOR, OPT_JAC_FD, OPT_BICG_TWORED, OPT_AMG_FALLBACK,
- OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+ OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
+ OPT_GMRES_RESTART) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
 PREC_BY_NAME = {"none": PREC_NONE, "nonprec": PREC_NONE, "ssor": PREC_SSOR, "ilu0": PREC_ILU0,
@@ -648,7 +649,8 @@ class Context:
 
     def linear_solve(self, rhs, prec=PREC_NONE, reduction=1e-8, maxit=20000, check_every=8,
                      method=0):
-        """method 0: ISTL BiCGSTABSolver, 1: ISTL CGSolver (METHOD_CG)."""
+        """method 0: ISTL BiCGSTABSolver, 1: ISTL CGSolver (METHOD_CG), 2 / 3: restarted GMRES /
+        flexible GMRES (METHOD_GMRES, METHOD_FGMRES; restart length OPT_GMRES_RESTART)."""
         rhs = self._vec(rhs)
         z = np.zeros_like(rhs)
         o = _SolveOpts(prec, reduction, maxit, check_every, method)
@@ -657,6 +659,16 @@ class Context:
         if rc not in (OK, E_BREAKDOWN):
             self._ck(rc)
         return z, {k: getattr(r, k) for k, _ in _SolveResult._fields_}
+
+    def solve_history(self):
+        """Residual norms of the last linear_solve when it was GMRES / FGMRES: [0] = |r0|, [k] the
+        norm after Arnoldi step k (iterations + 1 values); empty after BiCGSTAB / CG."""
+        n = C.c_int32(0)
+        self._ck(lib().pnp_solve_history(self.h, None, 0, C.byref(n)))
+        d = np.zeros(n.value)
+        if n.value:
+            self._ck(lib().pnp_solve_history(self.h, _ptr(d), n.value, C.byref(n)))
+        return d
 
     def prec_apply(self, d, prec):
         """v = M^{-1} d for one preconditioner application on the last assembled Jacobian."""

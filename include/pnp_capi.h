@@ -298,19 +298,36 @@ enum { PNP_PREC_NONE = 0, PNP_PREC_SSOR = 1, PNP_PREC_ILU0 = 2, PNP_PREC_JACOBI 
         * Level-scheduled on the GPU (one launch per dependency level, ~100-300 levels): a parity
         * mode, slower than the multicolour PNP_PREC_SSOR.  Block-Jacobi across ranks. */
        PNP_PREC_SSOR_NATURAL = 5 };
-enum { PNP_METHOD_BICGSTAB = 0, PNP_METHOD_CG = 1 };
+enum { PNP_METHOD_BICGSTAB = 0, PNP_METHOD_CG = 1,
+       /* Restarted GMRES(m), right-preconditioned (x = x0 + M^-1 V y): the monitored norm is the
+        * true residual's, so `reduction` means what it means for the other methods.  m =
+        * PNP_OPT_GMRES_RESTART.  Zero start; stops when the defect < reduction * defect0 or
+        * defect0 < 1e-30; iterations = it_half = Arnoldi steps (the SpMVs of the restarts are not
+        * counted), capped by maxit.  When the Givens estimate meets the test, x is formed and
+        * r = b - A x recomputed; a true norm that fails the test opens a new cycle; the reported
+        * defect is the recomputed one.  breakdown 5: a Hessenberg column that is zero or not
+        * finite (singular A M^-1).  Works with every preconditioner, in pnp_newton, with
+        * PNP_DEVICE_PTRS, on P_k and multi-rank contexts; not in reference-order mode, and
+        * PNP_OPT_GRAPH does not apply.  Unpreconditioned GMRES(30) stagnates on PNP Jacobians
+        * (DESIGN.md 4.8): use a preconditioner there. */
+       PNP_METHOD_GMRES = 2,
+       /* Flexible GMRES(m): the preconditioned basis Z is stored and x = x0 + Z y, so M may
+        * differ from application to application (PNP_OPT_ILU_F32 = 3).  m more vectors. */
+       PNP_METHOD_FGMRES = 3 };
 typedef struct {
   int32_t prec;       /* SSOR = one multicolour symmetric Gauss-Seidel sweep (k=1, w=1) */
   double reduction;   /* stop when ||r|| < reduction * ||r0|| (checked every half step) */
   int32_t maxit;
   int32_t check_every; /* host convergence poll period in iterations (0: default 8) */
-  int32_t method;     /* PNP_METHOD_BICGSTAB (ISTL BiCGSTABSolver, the default) or
+  int32_t method;     /* PNP_METHOD_BICGSTAB (ISTL BiCGSTABSolver, the default),
                          PNP_METHOD_CG (ISTL CGSolver: LINEARSOLVER CG_NOPREC / CG_Jacobi,
-                         src/instationary_pnp_from_pb_md.hh:198-206) */
+                         src/instationary_pnp_from_pb_md.hh:198-206), PNP_METHOD_GMRES or
+                         PNP_METHOD_FGMRES (restarted / flexible GMRES, see above) */
 } pnp_solve_opts;
 typedef struct {
   int32_t converged, iterations, breakdown; /* iterations = ceil(half-step counter); breakdown:
-      1 rho, 2 omega, 3 h (ISTL's 1e-80 tests), 4 diverged (PNP_PREC_AMG only) */
+      1 rho, 2 omega, 3 h (ISTL's 1e-80 tests), 4 diverged (PNP_PREC_AMG only), 5 GMRES: zero
+      or non-finite Hessenberg column */
   double it_half, defect0, defect, reduction, elapsed;
 } pnp_solve_result;
 
@@ -437,7 +454,10 @@ enum {
    * fp64 for the rest of that call (pnp_newton_result.precision_retries).  A rounded
    * preconditioner is a different M; the retry makes the fp64 preconditioner the fallback
    * whenever the cheaper one stalls.  0: a failed solve ends Newton as in ISTL. */
-  PNP_OPT_ILU_RETRY = 10
+  PNP_OPT_ILU_RETRY = 10,
+  /* Restart length m of PNP_METHOD_GMRES / PNP_METHOD_FGMRES: 2 .. 128, default 30.  The basis
+   * ((m + 1) vectors, FGMRES m more) is allocated at the first solve; changing m frees it. */
+  PNP_OPT_GMRES_RESTART = 11
 };
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
 
@@ -462,6 +482,14 @@ int pnp_linear_solve(pnp_ctx *ctx, const double *rhs, double *z, const pnp_solve
 /* pnp_linear_solve with flags (PNP_DEVICE_PTRS) */
 int pnp_linear_solve_ex(pnp_ctx *ctx, const double *rhs, double *z, const pnp_solve_opts *opts,
                         pnp_solve_result *res, int32_t flags);
+
+/* Residual history of the last pnp_linear_solve / pnp_linear_solve_ex on the context when it was
+ * a GMRES or FGMRES solve: defects[0] = ||r0||, defects[k] = the residual norm after Arnoldi step
+ * k -- the Givens estimate |g_{k+1}|; at each restart boundary and at the end the recomputed true
+ * norm.  *n = iterations + 1 (at most cap values are written; defects may be null with cap 0).
+ * After a BiCGSTAB or CG solve *n = 0.  Only the first 2^20 steps of a solve are kept (then
+ * *n = 2^20 + 1 and the last kept entry is not the final norm; pnp_solve_result.defect is). */
+int pnp_solve_history(pnp_ctx *ctx, double *defects, int32_t cap, int32_t *n);
 
 /* ---- Newton (PDELab Newton with hackbuschReuskenAcceptBest) -------------------------------- */
 typedef struct {

@@ -253,6 +253,22 @@ class BiCGStabBackend {
   InverseOperatorResult res_;
 };
 
+// PDELab's ISTLBackend_SEQ_GMRES_ILU0(maxiter, verbose, restart) (ISTL RestartedGMResSolver with
+// SeqILU0): restarted GMRES(restart) with the multicolour ILU(0), PNP_METHOD_GMRES.  The restart
+// length is a context option, set here; flexible = true gives PNP_METHOD_FGMRES.
+template <class V>
+class ISTLBackend_SEQ_GMRES_ILU0 : public BiCGStabBackend<V> {
+ public:
+  ISTLBackend_SEQ_GMRES_ILU0(Context &ctx, int maxiter = 5000, int verbose = 1, int restart = 200,
+                             bool flexible = false)
+      : BiCGStabBackend<V>(ctx, maxiter, PNP_PREC_ILU0, verbose,
+                           flexible ? PNP_METHOD_FGMRES : PNP_METHOD_GMRES) {
+    // PDELab's default restart (200) is above this library's cap of 128
+    check(pnp_set_option(ctx.get(), PNP_OPT_GMRES_RESTART, restart > 128 ? 128 : restart),
+          ctx.get());
+  }
+};
+
 // PDELab Newton with hackbuschReuskenAcceptBest; runs entirely through pnp_newton (the
 // residual, Jacobian and BiCGSTAB stay in HBM between steps)
 template <class V>
