@@ -306,6 +306,23 @@ struct pnp_ctx {
   DBuf<double> cvec, aux0, aux1;
   bool assembled = false;
   bool after_solve = false;  // a linear solve ran since the last Jacobian assembly (AsmArgs::cold)
+  // ---- matrix-free Jacobian application (PNP_OPT_MATRIX_FREE, jac_apply.hip) ----
+  // With the option on, a Jacobian "assembly" of a P1 analytic operator records the linearisation
+  // point (mf_x: the state with ghosts; mf_aa: the operator's arguments at that moment) and leaves
+  // the SELL values stale; halo_spmv and pnp_jacobian_apply compute J z from the point, and the
+  // consumers of vals (SSOR / ILU(0) / AMG set-up, the CSR view, the export) first run the
+  // ordinary assembly at the point (ensure_values).  mf_lin: the current Jacobian is held this
+  // way; vals_stale: vals does not hold it yet.
+  int mf_opt = 0;
+  bool mf_lin = false, vals_stale = false;
+  pnp::AsmArgs mf_aa{};
+  DBuf<double> mf_x, mf_r;  // the point; the residual ensure_values' fused assembly also writes
+  // Jacobi without SELL values: the diagonal blocks alone, one slot per chunk (launch_jac_diag),
+  // read by launch_jacobi through a layout whose chunk_off[c] = 64 c
+  DBuf<double> mf_diag;
+  DBuf<int> mf_choff;
+  bool mf_diag_valid = false;
+  long long mf_applies = 0, value_assemblies = 0;  // pnp_matfree_info
 
   // aggregation AMG (PNP_PREC_AMG, amg.h): the pattern hierarchy is built once per context (it
   // depends on the layout only), the coarse values after every assembly
@@ -410,11 +427,13 @@ struct pnp_ctx {
   }
   struct GraphKey {
     int count, prec, fuse, nf, pat, f32, flow;
+    int mf;  // the operator application: 0 the SpMV, 1 matrix-free, 2 matrix-free with the SELL
+             // values stale (Jacobi then reads the diagonal blocks of jacobi_prepare())
     const void *zout, *dmask;
     long long epoch;
     bool operator==(const GraphKey &o) const {
       return count == o.count && prec == o.prec && fuse == o.fuse && nf == o.nf && pat == o.pat &&
-             f32 == o.f32 && flow == o.flow && zout == o.zout && dmask == o.dmask &&
+             f32 == o.f32 && flow == o.flow && mf == o.mf && zout == o.zout && dmask == o.dmask &&
              epoch == o.epoch;
     }
   };
@@ -559,11 +578,22 @@ struct pnp_ctx {
     return PNP_OK;
   }
 
+  // the operator application on the rows of Lr (dl or one of its block subsets): the SpMV on the
+  // SELL values, or, with the Jacobian held as a linearisation point, the matrix-free kernel
+  hipError_t apply_op(const pnp::DevLayout &Lr, const double *vin, double *yout, int mode,
+                      const double *w, double *parts, int *nparts, hipStream_t s,
+                      const double *w2 = nullptr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+    if (mf_lin)
+      return pnp::launch_jac_apply(Lr, mf_aa, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);
+    return pnp::launch_spmv(Lr, nf, pat, vals.p, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);
+  }
+
   // halo exchange of vin's ghosts + y = A vin (mode / dots as launch_spmv).  Multi-GPU with the
   // split layout: the interior blocks (no ghost columns) run while the halo is in flight on
   // cstream, then the boundary blocks; their partials follow each other, *nsp counts both.
   int halo_spmv(double *vin, double *yout, int mode, const double *w, const double *w2, int *nsp) {
     hipError_t e;
+    if (mf_lin) mf_applies++;  // an interior + boundary pair counts once
     if (!split_spmv) {
       int rc = halo(vin, nf);
       if (rc) return rc;
@@ -573,8 +603,7 @@ struct pnp_ctx {
         t0 = ev_get();
         t1 = ev_get();
       }
-      e = pnp::launch_spmv(dl, nf, pat, vals.p, vin, yout, mode, w, partials.p, nsp, stream, w2,
-                           t0, t1);
+      e = apply_op(dl, vin, yout, mode, w, partials.p, nsp, stream, w2, t0, t1);
       if (e != hipSuccess) return hipfail(e, "spmv");
       if (t1) {
         ev_pending[T_SPMV].push_back({t0, t1});
@@ -587,7 +616,7 @@ struct pnp_ctx {
     int n1 = 0, n2 = 0, rc;
     if (lg || host_tr()) {  // in-process / host-staged transport: synchronous halo between the halves
       hipEvent_t t0 = tb(T_SPMV);
-      e = pnp::launch_spmv(dl_int, nf, pat, vals.p, vin, yout, mode, w, partials.p, &n1, stream, w2);
+      e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
       if (e != hipSuccess) return hipfail(e, "spmv interior");
       te(T_SPMV, t0);
       if ((rc = halo(vin, nf))) return rc;
@@ -598,15 +627,14 @@ struct pnp_ctx {
       if ((rc = halo_on(vin, nf, cstream))) return rc;
       if ((e = hipEventRecord(ev_halo, cstream)) != hipSuccess) return hipfail(e, "halo event");
       hipEvent_t t0 = tb(T_SPMV);
-      e = pnp::launch_spmv(dl_int, nf, pat, vals.p, vin, yout, mode, w, partials.p, &n1, stream, w2);
+      e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
       if (e != hipSuccess) return hipfail(e, "spmv interior");
       te(T_SPMV, t0);
       if ((e = hipStreamWaitEvent(stream, ev_halo, 0)) != hipSuccess)
         return hipfail(e, "halo wait");
     }
     hipEvent_t t1 = tb(T_SPMV);
-    e = pnp::launch_spmv(dl_bnd, nf, pat, vals.p, vin, yout, mode, w, partials.p + size_t(n1) * kd,
-                         &n2, stream, w2);
+    e = apply_op(dl_bnd, vin, yout, mode, w, partials.p + size_t(n1) * kd, &n2, stream, w2);
     if (e != hipSuccess) return hipfail(e, "spmv boundary");
     te(T_SPMV, t1);
     *nsp = n1 + n2;
@@ -818,8 +846,12 @@ struct pnp_ctx {
     if (kind < 0) return fail(PNP_E_STATE, "no operator set (pnp_set_operator)");
     int rc;
     if (jac && (rc = set_fd(fd_opt != 0))) return rc;
+    // matrix-free (P1, analytic): the Jacobian is the recorded point; only the residual the fused
+    // assembly would also have produced is computed now (Newton's right-hand side)
+    const bool mf = jac && mf_opt && degree == 1 && !fd_mode;
+    if (mf && (rc = mf_record(xdev))) return rc;
     aa.x = xdev;
-    aa.jac = fd_mode ? 0 : jac;
+    aa.jac = (fd_mode || mf) ? 0 : jac;
     aa.r = r.p;
     aa.cold = after_solve ? 1 : 0;
     // the P1 analytic assembly is one launch: it records its own start / end events (the
@@ -854,7 +886,66 @@ struct pnp_ctx {
       amg_valid = false;
       csr_vals_valid = false;
       after_solve = false;
+      mf_lin = vals_stale = mf;
+      mf_diag_valid = false;
+      if (!mf) value_assemblies++;
     }
+    return PNP_OK;
+  }
+
+  // the linearisation point of a matrix-free Jacobian: the state with its ghosts in a buffer of
+  // its own (a later residual overwrites x) and the operator's arguments as they are now
+  int mf_record(const double *xdev) {
+    const size_t nl = size_t(dl.n_local) * 3;
+    hipError_t e = hipSuccess;
+    if (mf_x.n < nl) e = mf_x.alloc(std::max<size_t>(1, nl));
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(mf_x.p, xdev, sizeof(double) * size_t(dl.n_local) * nf,
+                         hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return hipfail(e, "linearisation point");
+    mf_aa = aa;
+    mf_aa.x = mf_x.p;
+    mf_aa.jac = 1;
+    mf_aa.r = nullptr;
+    mf_aa.cold = 0;
+    return PNP_OK;
+  }
+
+  // the SELL values of a Jacobian held as a linearisation point, for whoever reads vals: the
+  // ordinary fused assembly at the point, once (its residual goes to a scratch vector)
+  int ensure_values() {
+    if (!mf_lin || !vals_stale) return PNP_OK;
+    const size_t no = size_t(L.n_owned) * 3;
+    hipError_t e = hipSuccess;
+    if (mf_r.n < no) e = mf_r.alloc(std::max<size_t>(1, no));
+    if (e != hipSuccess) return hipfail(e, "assemble at the linearisation point");
+    pnp::AsmArgs fa = mf_aa;
+    fa.r = mf_r.p;
+    fa.vals = vals.p;
+    fa.cold = after_solve ? 1 : 0;
+    hipEvent_t t0 = tb(T_ASM);
+    e = pnp::launch_assemble(dl, fa, stream);
+    if (e != hipSuccess) return hipfail(e, "assemble at the linearisation point");
+    te(T_ASM, t0);
+    vals_stale = false;
+    value_assemblies++;
+    return PNP_OK;
+  }
+
+  // Jacobi on a matrix-free Jacobian whose values were never needed: its diagonal blocks alone
+  int jacobi_prepare() {
+    if (!mf_lin || !vals_stale || mf_diag_valid) return PNP_OK;
+    hipError_t e = hipSuccess;
+    if (!mf_choff.p) {
+      std::vector<int> co(size_t(L.nchunks) + 1);
+      for (size_t c = 0; c < co.size(); c++) co[c] = int(c) * pnp::kRows;
+      int rc = upv(mf_choff, co, "diagonal layout");
+      if (rc) return rc;
+      e = mf_diag.alloc(std::max<size_t>(1, size_t(L.nchunks) * pnp::kRows * 6));
+    }
+    if (e == hipSuccess) e = pnp::launch_jac_diag(dl, mf_aa, mf_diag.p, stream);
+    if (e != hipSuccess) return hipfail(e, "jacobi diagonal");
+    mf_diag_valid = true;
     return PNP_OK;
   }
 
@@ -1181,6 +1272,7 @@ struct pnp_ctx {
     int rc;
     if ((rc = csr_structure())) return rc;
     if (csr_vals_valid) return nat_probe_run();
+    if ((rc = ensure_values())) return rc;
     hipError_t e = pnp::launch_csr_fill(dl, nf, pat, vals.p, csr_nnz, csr_src.p, csr_vidx.p,
                                         csr_val.p, stream);
     if (e != hipSuccess) return hipfail(e, "csr fill");
@@ -1752,6 +1844,7 @@ struct pnp_ctx {
   // three-pass path, the same bits)
   int ilu_factor() {
     if (lu_valid) return PNP_OK;
+    if (int rc = ensure_values()) return rc;
     hipEvent_t t0 = tb(T_FACT);
     hipError_t e;
     if (ilu_fused) {
@@ -1776,6 +1869,8 @@ struct pnp_ctx {
       lu_valid = false;
       return ilu_factor();
     }
+    if (which == 1)
+      if (int rc = ensure_values()) return rc;
     hipEvent_t t0 = tb(T_FACT);
     hipError_t e = pnp::launch_split(dl, nf, pat, which == 1 ? 1 : 0, which == 2 ? lu.p : vals.p,
                                      d_lsrc.p, (long long)d_lsrc.n, d_usrc.p, (long long)d_usrc.n,
@@ -1800,6 +1895,8 @@ struct pnp_ctx {
   int amg_setup() {
     int rc;
     if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
+    // the Galerkin products and the V-cycle's level-0 residuals read the SELL values
+    if ((rc = ensure_values())) return rc;
     if (!amg_built) {
       amg_d.clear();
       if (!pnp::amg_build(L, amg_opts.coarse_target, amg_opts.max_levels, amg_h, err))
@@ -1991,7 +2088,13 @@ struct pnp_ctx {
   // the single-level preconditioners, untimed, prerequisites (split / factors) in place
   int smoother(int prec, const double *d, double *vout) {
     hipError_t e = hipSuccess;
-    if (prec == PNP_PREC_JACOBI) {
+    if (prec == PNP_PREC_JACOBI && mf_lin && vals_stale) {
+      // no SELL values: the diagonal blocks of jacobi_prepare(), one slot per chunk
+      if (!mf_diag_valid) return fail(PNP_E_STATE, "Jacobi: no diagonal (jacobi_prepare)");
+      pnp::DevLayout dv = dl;
+      dv.chunk_off = mf_choff.p;
+      e = pnp::launch_jacobi(dv, nf, pat, mf_diag.p, d, vout, stream);
+    } else if (prec == PNP_PREC_JACOBI) {
       e = pnp::launch_jacobi(dl, nf, pat, vals.p, d, vout, stream);
     } else if (prec == PNP_PREC_SSOR) {
       e = pnp::launch_sgs(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, d, vout, tsgs.p,
@@ -2009,6 +2112,7 @@ struct pnp_ctx {
   // v = M^{-1} d over owned rows (v sized n_local)
   int precond(int prec, const double *d, double *vout) {
     int rc;
+    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
     if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
     if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
     if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
@@ -2063,6 +2167,7 @@ struct pnp_ctx {
     if (fixed > 0) check = fixed;
     int prec = o.prec;
     if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
+    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
     if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
     if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
     if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
@@ -2207,7 +2312,8 @@ struct pnp_ctx {
       const int glen = std::min(check, 16);
       while (graphs && glen > 1 && kend - k >= glen) {
         const GraphKey key{glen, prec, fuse ? 1 : 0, nf, pat, f32_now() + (ilu_y32() ? 4 : 0),
-                           ilu_flow_opt * 4 + (nat_flow_opt + 1), zout, dl.dmask, graph_epoch};
+                           ilu_flow_opt * 4 + (nat_flow_opt + 1),
+                           mf_lin ? (vals_stale ? 2 : 1) : 0, zout, dl.dmask, graph_epoch};
         bool captured = true;
         rc = graph_run(key, [&]() -> int {
           for (int i = 0; i < key.count; i++)
@@ -2358,6 +2464,7 @@ struct pnp_ctx {
     if (gm_hist.n < size_t(hcap) + 2) e = gm_hist.alloc(size_t(hcap) + 2);
     if (e != hipSuccess) return hipfail(e, "gmres history");
     if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
+    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
     if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
     if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
     if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
@@ -3666,6 +3773,7 @@ extern "C" int pnp_get_info(pnp_ctx *c, pnp_info *info) {
   b += c->vals.n * 8 + (c->x.n + c->r.n + c->rs.n + c->z.n + c->rt.n + c->p.n + c->v.n + c->t.n + c->y.n +
                         c->y2.n + c->b.n + c->prevu.n + c->ext.n) * 8 + c->ilu_y32buf.n * 4;
   b += c->d_colidx.n * 4 + c->d_rowmeta.n * 8 + c->d_xy.n * 8;
+  b += (c->mf_x.n + c->mf_r.n + c->mf_diag.n) * 8 + c->mf_choff.n * 4;  // PNP_OPT_MATRIX_FREE
   info->device_bytes = int64_t(b);
   return PNP_OK;
 }
@@ -3708,6 +3816,10 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   c->split_of = 0;
   c->amg_valid = false;
   c->csr_vals_valid = false;
+  c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
+  // a captured matrix-free application holds the operator's scalar arguments (dt, valency, ...) by
+  // value, which the graph key does not see
+  if (c->mf_opt) c->graphs_clear();
   // SELL padding slots point at the row itself and are never written by the assembly, so they
   // must hold zeros in the k-form layout of THIS operator (the SpMV multiplies them)
   CK(hipMemsetAsync(c->vals.p, 0, sizeof(double) * size_t(c->L.nslots) * c->nks, c->stream),
@@ -3872,6 +3984,9 @@ extern "C" int pnp_jacobian_export(pnp_ctx *c, int64_t *nnz, int32_t *rowptr, in
   total *= NV;
   *nnz = total;
   if (!rowptr || !col || !val) return PNP_OK;
+  hipSetDevice(c->device);
+  if (int rc = c->ensure_values()) return rc;  // a matrix-free Jacobian: assemble its values now
+  CK(hipStreamSynchronize(c->stream), "export");
   const int NKS = c->nks;
   std::vector<double> hv(size_t(L.nslots) * NKS);
   CK(hipMemcpy(hv.data(), c->vals.p, sizeof(double) * hv.size(), hipMemcpyDeviceToHost), "export");
@@ -3989,8 +4104,8 @@ extern "C" int pnp_jacobian_apply(pnp_ctx *c, const double *x, const double *z, 
   // z with ghosts (the halo of a global vector is local: every rank holds it), y = A z
   if ((rc = c->upload_ext(z, c->nf, c->y.p, true, dev))) return rc;
   int nsp = 0;
-  CK(pnp::launch_spmv(c->dl, c->nf, c->pat, c->vals.p, c->y.p, c->t.p, 0, nullptr, c->partials.p,
-                      &nsp, c->stream),
+  if (c->mf_lin) c->mf_applies++;
+  CK(c->apply_op(c->dl, c->y.p, c->t.p, 0, nullptr, c->partials.p, &nsp, c->stream),
      "jacobian apply");
   return c->download_ext(c->t.p, c->nf, y, dev);
 }
@@ -4150,7 +4265,27 @@ extern "C" int pnp_set_option(pnp_ctx *c, int32_t option, int64_t value) {
       c->seq_opt = int(value);
       c->assembled = false;  // the next Jacobian is assembled in the newly selected form
       c->csr_vals_valid = false;
+      c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
     }
+    return PNP_OK;
+  }
+  if (option == PNP_OPT_MATRIX_FREE) {
+    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_MATRIX_FREE takes 0 or 1");
+    if (value && c->degree > 1)
+      return c->fail(PNP_E_STATE,
+                     "PNP_OPT_MATRIX_FREE: P1 contexts only (the matrix-free application walks the "
+                     "P1 vertex fans; P_k contexts assemble)");
+    if (!value && c->mf_lin) {
+      // the current Jacobian goes on as an assembled one: its values, if nobody needed them yet
+      hipSetDevice(c->device);
+      if (int rc = c->ensure_values()) return rc;
+      c->mf_lin = c->mf_diag_valid = false;
+    }
+    // the graphs_clear() at the top of this function has dropped every captured BiCGSTAB graph
+    // and bumped graph_epoch: no graph captured in one form survives into the other, and none
+    // outlives an operator change made while the option was off (pnp_set_operator clears only
+    // while it is on)
+    c->mf_opt = int(value);
     return PNP_OK;
   }
   if (option == PNP_OPT_JAC_FD) {
@@ -4233,7 +4368,18 @@ extern "C" int pnp_get_option(pnp_ctx *c, int32_t option, int64_t *value) {
     *value = c->seq_opt;
     return PNP_OK;
   }
+  if (option == PNP_OPT_MATRIX_FREE) {
+    *value = c->mf_opt;
+    return PNP_OK;
+  }
   return c->fail(PNP_E_ARG, "unknown option");
+}
+
+extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_assemblies) {
+  if (!c) return PNP_E_ARG;
+  if (applies) *applies = c->mf_applies;
+  if (value_assemblies) *value_assemblies = c->value_assemblies;
+  return PNP_OK;
 }
 
 extern "C" int pnp_amg_configure(pnp_ctx *c, const pnp_amg_opts *o) {

@@ -328,6 +328,20 @@ hipError_t launch_spmv(const DevLayout &L, int nf, int pat, const double *vals, 
                        hipStream_t s, const double *w2 = nullptr, hipEvent_t t0 = nullptr,
                        hipEvent_t t1 = nullptr);
 
+// y = J(a.x) z over owned rows without a stored matrix (jac_apply.hip): the assembly's fan walk at
+// the linearisation point a (a.x with ghosts, frozen fields, dt, mask; a.r / a.vals are not
+// touched), each finished block multiplied by its neighbour's z instead of stored.  mode, w, w2,
+// partials, t0 / t1 and the block subsets of L (blkcount) as launch_spmv; *nparts = one group of
+// partials per workgroup (<= spmv_parts(n_owned))
+hipError_t launch_jac_apply(const DevLayout &L, const AsmArgs &a, const double *z, double *y,
+                            int mode, const double *w, double *partials, int *nparts,
+                            hipStream_t s, const double *w2 = nullptr, hipEvent_t t0 = nullptr,
+                            hipEvent_t t1 = nullptr);
+// the diagonal blocks of J(a.x) alone, unmasked k-form, one slot per chunk: chunk c's block of
+// lane l at dvals[64 NK c + vin(NK, q, l)] -- what launch_jacobi reads through a DevLayout whose
+// chunk_off[c] = 64 c.  dvals: 64 NK nchunks doubles
+hipError_t launch_jac_diag(const DevLayout &L, const AsmArgs &a, double *dvals, hipStream_t s);
+
 // preconditioners: v = M^{-1} d (v over owned rows)
 hipError_t launch_jacobi(const DevLayout &L, int nf, int pat, const double *vals, const double *d,
                          double *v, hipStream_t s);

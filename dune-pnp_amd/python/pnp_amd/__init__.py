@@ -35,7 +35,7 @@ PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL = rang
 METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES = 0, 1, 2, 3
 (OPT_ILU_F32, OPT_ILU_FUSED_FACTOR, OPT_JAC_FD, OPT_BICG_TWORED, OPT_AMG_FALLBACK,
  OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
- OPT_GMRES_RESTART) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11
+ OPT_GMRES_RESTART, OPT_MATRIX_FREE) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
 PREC_BY_NAME = {"none": PREC_NONE, "nonprec": PREC_NONE, "ssor": PREC_SSOR, "ilu0": PREC_ILU0,
@@ -790,6 +790,13 @@ class Context:
         self._ck(lib().pnp_get_option(self.h, int(option), C.byref(v)))
         return v.value
 
+    def matfree_info(self):
+        """OPT_MATRIX_FREE's counters since the context was created: matrix-free operator
+        applications launched, and assemblies that wrote the SELL values (in either mode)."""
+        a, v = C.c_int64(), C.c_int64()
+        self._ck(lib().pnp_matfree_info(self.h, C.byref(a), C.byref(v)))
+        return {"applies": a.value, "value_assemblies": v.value}
+
     def probe_slot_stores(self, tile_elems=256, reps=20):
         """pnp_probe_slot_stores (P_k contexts): the SELL slot stores of one Jacobian in SELL,
         spatial-tile and random row order; dict of the pnp_store_probe fields."""
@@ -816,3 +823,10 @@ def header_symbols():
     import re
     txt = open(HEADER).read()
     return sorted(set(re.findall(r"^\s*(?:int|void|const char \*)\s*(pnp_\w+)\s*\(", txt, re.M)))
+
+
+def header_constants():
+    """Enumerators `PNP_NAME = integer` of include/pnp_capi.h, as a dict."""
+    import re
+    txt = open(HEADER).read()
+    return {k: int(v) for k, v in re.findall(r"^\s*(PNP_\w+)\s*=\s*(-?\d+)\s*,?\s*$", txt, re.M)}

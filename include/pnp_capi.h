@@ -271,7 +271,9 @@ int pnp_jacobian_ex(pnp_ctx *ctx, const double *x, int32_t flags);
 /* GridOperator::jacobian_apply (the LOPs' NumericalJacobianApplyVolume, src/pnp_operator.hh:22-25):
  * y = J(x) z with J the matrix pnp_jacobian assembles (constrained rows identity).  x != NULL
  * assembles J(x) first (PNP_JAC_FD: by forward differences); x == NULL applies the last
- * assembled Jacobian.  z, y: external layout, nfields*nv; PNP_DEVICE_PTRS for device vectors. */
+ * assembled Jacobian.  z, y: external layout, nfields*nv; PNP_DEVICE_PTRS for device vectors.
+ * With PNP_OPT_MATRIX_FREE = 1 no matrix is assembled: x sets the linearisation point and the
+ * product is computed from it (x == NULL: from the point of the last Jacobian). */
 int pnp_jacobian_apply(pnp_ctx *ctx, const double *x, const double *z, double *y, int32_t flags);
 /* device CSR view of the last assembled Jacobian (the ISTL BCRSMatrix<1x1> the reference's
  * solvers take): external layout, sorted columns, the stored block pattern (structurally zero
@@ -457,9 +459,32 @@ enum {
   PNP_OPT_ILU_RETRY = 10,
   /* Restart length m of PNP_METHOD_GMRES / PNP_METHOD_FGMRES: 2 .. 128, default 30.  The basis
    * ((m + 1) vectors, FGMRES m more) is allocated at the first solve; changing m frees it. */
-  PNP_OPT_GMRES_RESTART = 11
+  PNP_OPT_GMRES_RESTART = 11,
+  /* 1: matrix-free Jacobian application (jac_apply.hip).  P1 contexts
+   * (pnp_create), every operator, the analytic Jacobian.  A Jacobian assembly (pnp_jacobian[_ex],
+   * pnp_jacobian_apply with x, Newton's per-step assembly, pnp_assemble_state) then only records
+   * the linearisation point -- the state with its ghosts, in a buffer of its own, and the
+   * operator's arguments -- and computes the residual; the operator application inside every
+   * Krylov method and in pnp_jacobian_apply walks the assembly's vertex fans at that point and
+   * multiplies each finished block by its neighbour's z instead of storing it.  The SELL values
+   * are assembled, at the recorded point, only when something reads them: the SSOR, ILU(0), AMG
+   * and natural-order SSOR set-up, pnp_jacobian_export, pnp_jacobian_csr_device.  So every
+   * preconditioner, export and view works as before, and solves with PNP_PREC_NONE or
+   * PNP_PREC_JACOBI (which takes the diagonal blocks from a walk of its own), Newton included,
+   * never write the matrix (pnp_matfree_info counts).  Ignored, with the assembled path taken,
+   * for forward-difference Jacobians (PNP_OPT_JAC_FD, PNP_JAC_FD) and in reference-order mode
+   * (PNP_OPT_SEQ_ORDER).  On a P_k context of degree > 1 setting 1 returns PNP_E_STATE.  Turning
+   * it off assembles the values of the current Jacobian if nobody had needed them yet.
+   * 0 (default): the assembled SELL matrix and its SpMV, as before. */
+  PNP_OPT_MATRIX_FREE = 12
 };
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
+/* PNP_OPT_MATRIX_FREE's counters, since the context was created.  applies: matrix-free operator
+ * applications launched (the interior + boundary pair of a halo-overlapped application counts
+ * once, as does an application captured into a replayed graph).  value_assemblies: assemblies
+ * that wrote the SELL values, in either mode (with the option off: every Jacobian assembly).
+ * Either pointer may be NULL. */
+int pnp_matfree_info(pnp_ctx *ctx, int64_t *applies, int64_t *value_assemblies);
 
 /* ---- creation options (process-wide; read by every later pnp_create / pnp_create_pk /
  * pnp_layout_build, since the row colouring and the layout are built at creation) ------------ */

@@ -186,6 +186,12 @@ class GridOperator {
     numerical_ = on;
     check(pnp_set_option(ctx_.get(), PNP_OPT_JAC_FD, on ? 1 : 0), ctx_.get());
   }
+  // matrix-free operator application (PNP_OPT_MATRIX_FREE; P1 contexts, the analytic Jacobian):
+  // jacobian() then records the linearisation point, jacobian_apply and the Krylov solvers compute
+  // J z from it, and the matrix is assembled only if a preconditioner, export or view reads it
+  void setMatrixFree(bool on) {
+    check(pnp_set_option(ctx_.get(), PNP_OPT_MATRIX_FREE, on ? 1 : 0), ctx_.get());
+  }
   Context &context() const { return ctx_; }
 
  private:
