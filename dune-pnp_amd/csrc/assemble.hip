@@ -28,17 +28,22 @@ namespace {
 
 // store one block's coefficients (k-form, OpTraits::NK values, unmasked: the Dirichlet rows are
 // applied by the consumers, see kernels.h expand_k / mask_rows)
-template <int OP>
+// KC (PNP): the slot's first 16-B record (k0, k1: geometry and l_b only) already holds this
+// operator's values and is left alone; records 1.. are written -- (k2, k3) as one dwordx4 and
+// k4.  Kc[0] and Kc[1] are not read.  The record is 1 KiB per 64-row slot, whole 128-B lines.
+template <int OP, int KC = 0>
 __device__ __forceinline__ void store_block(double *__restrict__ vc, int lane, int s,
                                             const double *Kc) {
   constexpr int NK = OpTraits<OP>::NK;
+  static_assert(!KC || OP == OP_PNP, "constant planes: the PNP operator only");
+  constexpr int Q0 = KC ? 2 : 0;
   // non-temporal: the blocks are read back only by later kernels (SpMV, split), which stream
   // them non-temporally too; plain stores allocate the 207 MB in the caches and evict the
   // gathered x / xy / column indices.  94 -> 77 us at config 3 (profiles/r01/ab_asm_nt_stores.log)
 #ifdef ASM_STORE_PLAIN  // A/B build flag: plain (allocating) block stores
-  store_vals<NK>(vc + size_t(s) * NK * kRows, lane, Kc);
+  store_vals<NK, Q0>(vc + size_t(s) * NK * kRows, lane, Kc);
 #else
-  store_vals_nt<NK>(vc + size_t(s) * NK * kRows, lane, Kc);
+  store_vals_nt<NK, Q0>(vc + size_t(s) * NK * kRows, lane, Kc);
 #endif
 }
 
@@ -217,7 +222,20 @@ __host__ __device__ constexpr int asm_lds_rec() {  // doubles per staged column
   return 2 + OpTraits<OP>::NF + (OP == OP_DIFF || OP == OP_DIFF_IE || OP == OP_POISSON) +
          (OP == OP_POISSON);
 }
-template <int OP, int JAC, int MINW, int FANR, int SPLIT = FANR, int STAGE = 0, int LDSG = 0>
+// KC (PNP, JAC): the block coefficients k0 / k1 depend on the mesh and l_b only, so the planes
+// an earlier full assembly of this operator stored are still right (AsmArgs::kconst, kept by the
+// context): this instantiation neither accumulates nor stores them (store_block), 82.5 of the
+// 207 MB write stream at config 3.  k2.. and the residual are computed as without KC, bitwise.
+// 148 VGPRs, no spill, 3 waves per SIMD; at 4 waves (128 VGPRs) it spills 33-36 VGPRs and runs
+// 74 us warm against 44.  PNP_IE has the same planes (scaled by dt), but there the compiler
+// contracts k2..k4 differently without the k0 / k1 accumulators (one ulp in a few blocks), so it
+// keeps writing every plane.
+template <int OP>
+constexpr int asm_kc() {  // 1: the operator's blocks have state-independent planes
+  return OP == OP_PNP;
+}
+template <int OP, int JAC, int MINW, int FANR, int SPLIT = FANR, int STAGE = 0, int LDSG = 0,
+          int KC = 0>
 __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs a) {
   using T = OpTraits<OP>;
   constexpr int NF = T::NF, NK = T::NK, NS = FANR;
@@ -345,7 +363,7 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
       for (int v = 0; v < NK; v++) stg[((s - 1) * NK + v) * 256 + threadIdx.x] = Kc[v];
       staged |= 1u << s;
     } else {
-      store_block<OP>(vc, lane, s, Kc);
+      store_block<OP, KC>(vc, lane, s, Kc);
     }
   };
 #pragma unroll
@@ -360,7 +378,7 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
             double K[NK];
 #pragma unroll
             for (int v = 0; v < NK; v++) K[v] = stg[((q - 1) * NK + v) * 256 + threadIdx.x];
-            store_block<OP>(vc, lane, q, K);
+            store_block<OP, KC>(vc, lane, q, K);
           }
       }
     }
@@ -382,8 +400,8 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
         double Ct[NK];
 #pragma unroll
         for (int v = 0; v < NK; v++) Ct[v] = 0;
-        element<OP, JAC>(a, G, pi2.y, pn[s].y, pt.y, ui, un[s], ut, ai, a0[s], at0, aq, a1[s],
-                         at1, R, D, P, Ct);
+        element<OP, JAC, KC>(a, G, pi2.y, pn[s].y, pt.y, ui, un[s], ut, ai, a0[s], at0, aq,
+                             a1[s], at1, R, D, P, Ct);
         if constexpr (JAC) {
           if (s == 1 && closed) {
 #pragma unroll
@@ -405,9 +423,9 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
     if (closed) {
 #pragma unroll
       for (int v = 0; v < NK; v++) F[v] += P[v];
-      store_block<OP>(vc, lane, 1, F);
+      store_block<OP, KC>(vc, lane, 1, F);
     }
-    store_block<OP>(vc, lane, 0, D);
+    store_block<OP, KC>(vc, lane, 0, D);
   }
 #pragma unroll
   for (int f = 0; f < NF; f++) {
@@ -588,6 +606,14 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 2, 9>), grid, block, 0, s, t0, t1, 0, L, a);  \
     else if (ga == 3 && fanr == 9)                                                 \
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 5>), grid, block, 0, s, t0, t1, 0, L, a); \
+    else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst &&                   \
+             lds_walk(OpTraits<OPK>::NK) && L.uown &&                               \
+             size_t(L.unmax) * asm_lds_rec<OPK>() * 8 <= 53 * 1024)                    \
+      hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 1, asm_kc<OPK>()>), grid,  \
+                         block, size_t(L.unmax) * asm_lds_rec<OPK>() * 8, s, t0, t1, 0, L, a); \
+    else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst)                    \
+      hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 0, asm_kc<OPK>()>), grid,  \
+                         block, 0, s, t0, t1, 0, L, a);                             \
     else if (ga == 4 && fanr == 9 && lds_walk(OpTraits<OPK>::NK) && L.uown &&       \
              size_t(L.unmax) * asm_lds_rec<OPK>() * 8 <= 53 * 1024)                    \
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 1>), grid, block,         \

@@ -323,6 +323,31 @@ struct pnp_ctx {
   DBuf<int> mf_choff;
   bool mf_diag_valid = false;
   long long mf_applies = 0, value_assemblies = 0;  // pnp_matfree_info
+  // ---- state-independent planes of the PNP k-form (PNP_OPT_ASM_REUSE_CONST) ----
+  // k0 / k1 of every PNP block depend on the mesh and the parameters only.
+  // vals_const_valid: vals holds them for the operator set now -- set by a P1 analytic assembly
+  // that wrote every plane, cleared by whatever else zeroes or writes vals (pnp_set_operator,
+  // set_fd, the FD and P_k Jacobians).  While it holds, the PNP Jacobian assembly leaves those
+  // planes alone (AsmArgs::kconst).
+  int asm_reuse_opt = [] {  // the environment variable PNP_ASM_REUSE_CONST=0/1 sets the default
+    const char *e = std::getenv("PNP_ASM_REUSE_CONST");
+    return (e && std::atoi(e) == 0) ? 0 : 1;
+  }();
+  bool vals_const_valid = false;
+  long long asm_full = 0, asm_reused = 0;  // pnp_asm_info
+  bool asm_kconst() const {
+    return asm_reuse_opt && vals_const_valid && degree == 1 && !fd_mode && kind == PNP_OP_PNP;
+  }
+  // bookkeeping after a launch that wrote vals: kc = it relied on the stored constant planes,
+  // full = it was the P1 analytic assembly writing every plane
+  void asm_wrote(bool kc, bool full) {
+    if (kc) {
+      asm_reused++;
+    } else {
+      asm_full++;
+      vals_const_valid = full;
+    }
+  }
 
   // aggregation AMG (PNP_PREC_AMG, amg.h): the pattern hierarchy is built once per context (it
   // depends on the layout only), the coarse values after every assembly
@@ -854,6 +879,7 @@ struct pnp_ctx {
     aa.jac = (fd_mode || mf) ? 0 : jac;
     aa.r = r.p;
     aa.cold = after_solve ? 1 : 0;
+    aa.kconst = (aa.jac && asm_kconst()) ? 1 : 0;
     // the P1 analytic assembly is one launch: it records its own start / end events (the
     // kernel's duration, as the kernel trace reports it); the other forms take an event pair
     const bool one = degree == 1 && !(jac && fd_mode);
@@ -872,7 +898,11 @@ struct pnp_ctx {
     if (e == hipSuccess && jac && fd_mode && degree == 1)
       e = pnp::launch_fd_jacobian(dl, aa, nf, pat, fd_ne, fd_etri.p, fd_rptr.p, fd_cdata.p,
                                   fd_jel.p, stream);
-    if (e != hipSuccess) return hipfail(e, "assemble");
+    if (e != hipSuccess) {
+      if (jac && !mf) vals_const_valid = false;
+      return hipfail(e, "assemble");
+    }
+    if (jac && !mf) asm_wrote(aa.kconst != 0, degree == 1 && !fd_mode);
     if (t1) {
       ev_pending[T_ASM].push_back({t0, t1});
       t_n[T_ASM]++;
@@ -923,9 +953,14 @@ struct pnp_ctx {
     fa.r = mf_r.p;
     fa.vals = vals.p;
     fa.cold = after_solve ? 1 : 0;
+    fa.kconst = asm_kconst() ? 1 : 0;
     hipEvent_t t0 = tb(T_ASM);
     e = pnp::launch_assemble(dl, fa, stream);
-    if (e != hipSuccess) return hipfail(e, "assemble at the linearisation point");
+    if (e != hipSuccess) {
+      vals_const_valid = false;
+      return hipfail(e, "assemble at the linearisation point");
+    }
+    asm_wrote(fa.kconst != 0, true);
     te(T_ASM, t0);
     vals_stale = false;
     value_assemblies++;
@@ -1611,6 +1646,7 @@ struct pnp_ctx {
     lu_valid = false;
     split_of = 0;
     amg_valid = false;
+    vals_const_valid = false;  // another value layout, zeroed below
     if (on && degree == 1) {
       // one-step operators keep two matrices per element (spatial, temporal: fd_jacobian.hip)
       const size_t need = size_t(fd_ne) * 9 * nf * nf * 2;
@@ -3822,6 +3858,7 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   if (c->mf_opt) c->graphs_clear();
   // SELL padding slots point at the row itself and are never written by the assembly, so they
   // must hold zeros in the k-form layout of THIS operator (the SpMV multiplies them)
+  c->vals_const_valid = false;
   CK(hipMemsetAsync(c->vals.p, 0, sizeof(double) * size_t(c->L.nslots) * c->nks, c->stream),
      "clear matrix");
   const pnp::Mesh &m = c->mesh;
@@ -4288,6 +4325,12 @@ extern "C" int pnp_set_option(pnp_ctx *c, int32_t option, int64_t value) {
     c->mf_opt = int(value);
     return PNP_OK;
   }
+  if (option == PNP_OPT_ASM_REUSE_CONST) {
+    if (value != 0 && value != 1)
+      return c->fail(PNP_E_ARG, "PNP_OPT_ASM_REUSE_CONST takes 0 or 1");
+    c->asm_reuse_opt = int(value);  // vals holds every plane either way: nothing to invalidate
+    return PNP_OK;
+  }
   if (option == PNP_OPT_JAC_FD) {
     if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_JAC_FD takes 0 or 1");
     c->fd_opt = int(value);
@@ -4372,6 +4415,10 @@ extern "C" int pnp_get_option(pnp_ctx *c, int32_t option, int64_t *value) {
     *value = c->mf_opt;
     return PNP_OK;
   }
+  if (option == PNP_OPT_ASM_REUSE_CONST) {
+    *value = c->asm_reuse_opt;
+    return PNP_OK;
+  }
   return c->fail(PNP_E_ARG, "unknown option");
 }
 
@@ -4379,6 +4426,13 @@ extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_ass
   if (!c) return PNP_E_ARG;
   if (applies) *applies = c->mf_applies;
   if (value_assemblies) *value_assemblies = c->value_assemblies;
+  return PNP_OK;
+}
+
+extern "C" int pnp_asm_info(pnp_ctx *c, int64_t *full, int64_t *reused) {
+  if (!c) return PNP_E_ARG;
+  if (full) *full = c->asm_full;
+  if (reused) *reused = c->asm_reused;
   return PNP_OK;
 }
 

@@ -91,7 +91,9 @@ __device__ __forceinline__ void pb_fifth(double u, double &e, double &ei) {
 }
 
 // Contributions of element (i, b, c) to row i: residual res[NF], blocks (i,i), (i,b), (i,c).
-template <int OP, int JAC>
+// KC (PNP): the state-independent coefficients k0 and k1 are not accumulated (the
+// assembly that leaves their stored planes alone, assemble.hip); the others are untouched.
+template <int OP, int JAC, int KC = 0>
 __device__ __forceinline__ void element(const AsmArgs &a, const Geo &G, double yi, double yb,
                                         double yc, const double *ui, const double *ub,
                                         const double *uc, double pi_, double pb_, double pc_,
@@ -126,8 +128,10 @@ __device__ __forceinline__ void element(const AsmArgs &a, const Geo &G, double y
     }
     if constexpr (JAC) {
       auto blk = [&](double *B, double Gij, double Mij, double mj, double M2ij) {
-        B[0] += sc * Gij * I.W;
-        B[1] += sc * kap * Mij;
+        if constexpr (!KC) {
+          B[0] += sc * Gij * I.W;
+          B[1] += sc * kap * Mij;
+        }
         B[2] += sc * Gij * Sp;
         B[3] += sc * Gij * Sm;
         B[4] += sc * gp * mj;

@@ -109,19 +109,22 @@ __device__ __forceinline__ void load_vals_nt(const double *__restrict__ sb, int 
   if constexpr (NV & 1) B[NV - 1] = __builtin_nontemporal_load(sb + (NV - 1) * kRows + lane);
 }
 
-template <int NV>
+template <int NV, int Q0 = 0>
 __device__ __forceinline__ void store_vals(double *__restrict__ sb, int lane, const double *B) {
+  static_assert(Q0 % 2 == 0 && Q0 < NV, "whole 16-B records only");
 #pragma unroll
-  for (int q = 0; q + 1 < NV; q += 2)
+  for (int q = Q0; q + 1 < NV; q += 2)
     reinterpret_cast<double2 *>(sb + (q >> 1) * 2 * kRows)[lane] = make_double2(B[q], B[q + 1]);
   if constexpr (NV & 1) sb[(NV - 1) * kRows + lane] = B[NV - 1];
 }
 
-template <int NV>
+// Q0 (even): the first value written; the records of values 0 .. Q0-1 are left as they are
+template <int NV, int Q0 = 0>
 __device__ __forceinline__ void store_vals_nt(double *__restrict__ sb, int lane, const double *B) {
+  static_assert(Q0 % 2 == 0 && Q0 < NV, "whole 16-B records only");
   typedef double d2v __attribute__((ext_vector_type(2)));
 #pragma unroll
-  for (int q = 0; q + 1 < NV; q += 2) {
+  for (int q = Q0; q + 1 < NV; q += 2) {
     d2v t;
     t.x = B[q];
     t.y = B[q + 1];
@@ -293,6 +296,8 @@ struct AsmArgs {
   double *vals;          // SELL values
   int cold;              // 1: the launch follows a linear solve (Newton's Jacobian): its inputs are
                          // out of the caches, and the Jacobian takes the LDS-staged walk
+  int kconst;            // 1 (PNP, jac): the state-independent planes k0 / k1 in vals are
+                         // those of this operator already, and the launch may leave them alone
 };
 
 // BiCGSTAB scalar block, resident on the device (no host round trip per half step)

@@ -10,6 +10,8 @@
 //                 [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec ...] [--amg-smoother s]
 //                 [--device d] [--out prefix]
 //                 [--matrix-free]  (PNP_OPT_MATRIX_FREE on every context: P1 only)
+//                 [--asm-full]  (PNP_OPT_ASM_REUSE_CONST = 0: every PnpOperator Jacobian assembly writes the
+//                                 state-independent planes too)
 //                 [--method bicgstab|cg|gmres|fgmres] [--restart m]  (the PNP phases' Krylov method,
 //                                 default bicgstab; m: the GMRES restart length, 2 .. 128, default 30)
 //                 [--md-reduction r]
@@ -57,7 +59,7 @@ static void usage() {
   std::printf(
       "usage: pnp_main <config.cfg> [--refine k] [--mesh-scale s] [--mode stationary|instationary|md|pb]\n"
       "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec p]\n"
-      "                [--device d] [--matrix-free]\n"
+      "                [--device d] [--matrix-free] [--asm-full]\n"
       "                [--method bicgstab|cg|gmres|fgmres] [--restart m]\n"
       "                [--amg-smoother ssor|ilu0|jacobi]\n"
       "                [--out prefix] [--md-reduction r]\n"
@@ -190,7 +192,7 @@ int main(int argc, char **argv) {
   std::string cfgfile = argv[1], mode = "stationary", prec = "ssor", pb_prec = "ssor", out;
   std::string amg_smoother;  // empty: SSOR for the PB phase, ILU(0) for the PNP phases
   int refine = 0, steps = -1, device = -1, degree = 1;
-  bool ref_order = false, matrix_free = false;
+  bool ref_order = false, matrix_free = false, asm_full = false;
   double mesh_scale = 1.0;  // size scale when the mesh comes from a .geo (gmsh -clscale)
   double md_reduction = -1;  // md mode: override the linear reductions (1e-5 diffusion, 1e-10 Poisson)
   // Newton absolute limit (PDELab NewtonTerminate abs_limit, default 1e-12 as in PDELab); the
@@ -223,6 +225,7 @@ int main(int argc, char **argv) {
     else if (a == "--method") method = next();
     else if (a == "--restart") restart = std::atoi(next().c_str());
     else if (a == "--matrix-free") matrix_free = true;
+    else if (a == "--asm-full") asm_full = true;
     else if (a == "--reference-solvers") {
       pb_prec = "ssor_natural";
       prec = "none";
@@ -280,6 +283,7 @@ int main(int argc, char **argv) {
     if (ref_order) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_SEQ_ORDER, 1), ctx.get());
     // operator applications computed from the linearisation state instead of the assembled matrix
     if (matrix_free) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_MATRIX_FREE, 1), ctx.get());
+    if (asm_full) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_ASM_REUSE_CONST, 0), ctx.get());
     const int newton_verbosity = rank == 0 ? (ref_order ? 2 : 1) : 0;
     int nv = ctx.nv();  // DOF nodes of the P_degree space
     if (rank == 0)

@@ -35,7 +35,8 @@ PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL = rang
 METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES = 0, 1, 2, 3
 (OPT_ILU_F32, OPT_ILU_FUSED_FACTOR, OPT_JAC_FD, OPT_BICG_TWORED, OPT_AMG_FALLBACK,
  OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
- OPT_GMRES_RESTART, OPT_MATRIX_FREE) = 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12
+ OPT_GMRES_RESTART, OPT_MATRIX_FREE, OPT_ASM_REUSE_CONST) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11,
+                                                             12, 13)
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
 PREC_BY_NAME = {"none": PREC_NONE, "nonprec": PREC_NONE, "ssor": PREC_SSOR, "ilu0": PREC_ILU0,
@@ -796,6 +797,14 @@ class Context:
         a, v = C.c_int64(), C.c_int64()
         self._ck(lib().pnp_matfree_info(self.h, C.byref(a), C.byref(v)))
         return {"applies": a.value, "value_assemblies": v.value}
+
+    def asm_info(self):
+        """Jacobian assemblies since the context was created that wrote every plane of the SELL
+        values, and PNP assemblies that kept the stored state-independent planes
+        (OPT_ASM_REUSE_CONST)."""
+        f, r = C.c_int64(), C.c_int64()
+        self._ck(lib().pnp_asm_info(self.h, C.byref(f), C.byref(r)))
+        return {"full": f.value, "reused": r.value}
 
     def probe_slot_stores(self, tile_elems=256, reps=20):
         """pnp_probe_slot_stores (P_k contexts): the SELL slot stores of one Jacobian in SELL,

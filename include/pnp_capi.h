@@ -476,9 +476,25 @@ enum {
    * (PNP_OPT_SEQ_ORDER).  On a P_k context of degree > 1 setting 1 returns PNP_E_STATE.  Turning
    * it off assembles the values of the current Jacobian if nobody had needed them yet.
    * 0 (default): the assembled SELL matrix and its SpMV, as before. */
-  PNP_OPT_MATRIX_FREE = 12
+  PNP_OPT_MATRIX_FREE = 12,
+  /* 1 (default): the Jacobian assembly of PnpOperator (P1, analytic) writes the state-independent
+   * coefficients of its blocks once per operator.  Of the five stored k-form values per block,
+   * k0 = sum G_ij W and k1 = sum kappa M_ij -- the linear Poisson row -- depend on the mesh and
+   * the parameters only, and they are the first 16-B record of every SELL slot.  The first
+   * assembly after pnp_set_operator (or after anything else that rewrites the values, such as a
+   * forward-difference Jacobian) writes every plane; the following ones leave that record alone
+   * and write the state-dependent values and the residual: 82.5 of the 207 MB written per launch
+   * at config 3.  The stored matrix is bit for bit that of 0.  PnpTOperator
+   * (implicit Euler) writes all planes on every assembly.  0: every Jacobian assembly writes all
+   * planes (the environment variable PNP_ASM_REUSE_CONST=0/1 sets the default).  pnp_asm_info
+   * counts both. */
+  PNP_OPT_ASM_REUSE_CONST = 13
 };
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
+/* Jacobian assemblies that wrote the SELL values, since the context was created.  full: those that
+ * wrote every plane (every form and operator); reused: PNP assemblies that kept the
+ * stored constant planes (PNP_OPT_ASM_REUSE_CONST).  Either pointer may be NULL. */
+int pnp_asm_info(pnp_ctx *ctx, int64_t *full, int64_t *reused);
 /* PNP_OPT_MATRIX_FREE's counters, since the context was created.  applies: matrix-free operator
  * applications launched (the interior + boundary pair of a halo-overlapped application counts
  * once, as does an application captured into a replayed graph).  value_assemblies: assemblies
