@@ -47,6 +47,27 @@ __device__ __forceinline__ void store_block(double *__restrict__ vc, int lane, i
 #endif
 }
 
+// r = mask(R + cvec) of one row.  fl = the row's flag byte (AsmArgs::rowflag): the constant load is
+// zero except on flux-boundary rows (and on every row of an implicit Euler operator), so only
+// flagged rows read cvec; the others add the +0.0 the load would have returned (the add stays:
+// -0.0 + 0.0 = +0.0).  The mask is the flag's low bits.
+template <int NF>
+__device__ __forceinline__ void residual_tail(const AsmArgs &a, int row, unsigned fl,
+                                              const double (&R)[NF]) {
+  double cv[NF];
+#pragma unroll
+  for (int f = 0; f < NF; f++) cv[f] = 0.0;
+  if (fl & kRowFlagLoad) {
+#pragma unroll
+    for (int f = 0; f < NF; f++) cv[f] = a.cvec[size_t(row) * NF + f];
+  }
+#pragma unroll
+  for (int f = 0; f < NF; f++) {
+    const double rv = R[f] + cv[f];
+    a.r[size_t(row) * NF + f] = ((fl >> f) & 1) ? 0.0 : rv;
+  }
+}
+
 // One thread per owned vertex row.  JAC = 0: residual only (Newton line search).
 // FANR > 0: the row's column indices (fans of at most FANR - 1 neighbours) are loaded once into
 // registers, so the fan walk issues no dependent index loads.  On gfx9-family ISAs vmcnt counts
@@ -190,12 +211,7 @@ __global__ __launch_bounds__(256, MINW) void k_assemble(DevLayout L, AsmArgs a) 
     }
     store_block<OP>(vc, lane, 0, D);
   }
-#pragma unroll
-  for (int f = 0; f < NF; f++) {
-    const size_t q = size_t(row) * NF + f;
-    const double rv = R[f] + a.cvec[q];
-    a.r[q] = a.dmask[q] != 0 ? 0.0 : rv;
-  }
+  residual_tail<NF>(a, row, a.rowflag[row], R);
 }
 
 // Gather-all variant (GA): every neighbour's data (coordinates, NF dofs, frozen fields) of the
@@ -234,205 +250,309 @@ template <int OP>
 constexpr int asm_kc() {  // 1: the operator's blocks have state-independent planes
   return OP == OP_PNP;
 }
+// PIPE (PNP_ASM_PIPE=1; off by default): a persistent grid of G workgroups (G a multiple of 8,
+// so a workgroup stays on its XCD's spatial slice); workgroup b walks the logical 256-row tiles
+// b, b + G, ... of row_block().  Every wave is on its own (no barrier, atomic or flag).  While a wave walks tile t,
+// the per-row inputs of its 64 rows of the next tile -- 8 column indices, the two rowmeta dwords
+// and the flag byte's dword -- are on their way into the wave's own kPipeDw * 256 bytes of LDS by
+// LDS-DMA, issued once the wave has read tile t's values out of that region (one buffer per wave).
+// The wave-uniform block map entries and chunk offsets run two tiles ahead in scalar registers.
+// At the top of a tile the wave reads its indices from LDS and issues its own xy / x loads and
+// the slot 1 .. SPLIT-1 gathers together: one exposed round trip per tile instead of four in
+// sequence (blkmap, chunk_off, rowmeta + indices, gathers).  The walk itself is the same code:
+// 166 VGPRs, no spill, the direct walk's fp64 instruction multiset, bitwise its results.
+// Measured at config 3 it is slower, 44.1 us warm against 39.6, at every grid size: the wait for
+// the DMA loads is a wait for the previous tile's stores too (vmcnt retires in issue order), and
+// a resident grid walks 4 tiles where dynamic dispatch balances to 3.75.
+constexpr int kPipeDw = 11;  // dwords per lane of the prefetch region
+template <class P>
+__device__ __forceinline__ void lds_dma4(const P *src, uint32_t *dst_wave) {
+  // 4 bytes per lane from src (per lane) to dst_wave (wave-uniform) + 4 * lane
+  __builtin_amdgcn_global_load_lds(
+      (const __attribute__((address_space(1))) void *)(src),
+      (__attribute__((address_space(3))) void *)(dst_wave), 4, 0, 0);
+}
+// a wave-uniform load of layout data that no kernel writes: from the constant address space, so
+// it is a scalar load whatever the kernel stores in between
+__device__ __forceinline__ int const_ld(const int *p, int i) {
+  return ((const __attribute__((address_space(4))) int *)(p))[i];
+}
+__device__ __forceinline__ int row_block_const(const DevLayout &L, int b, int nwg) {  // row_block
+  return L.blkmap ? const_ld(L.blkmap, xcd_block(b, nwg, 1)) : xcd_block(b, nwg, L.xcd_remap);
+}
 template <int OP, int JAC, int MINW, int FANR, int SPLIT = FANR, int STAGE = 0, int LDSG = 0,
-          int KC = 0>
+          int KC = 0, int PIPE = 0>
 __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs a) {
   using T = OpTraits<OP>;
   constexpr int NF = T::NF, NK = T::NK, NS = FANR;
   constexpr bool AUX0 = OP == OP_DIFF || OP == OP_DIFF_IE || OP == OP_POISSON;
   constexpr bool AUX1 = OP == OP_POISSON;
   constexpr int RW = asm_lds_rec<OP>();
+  static_assert(!PIPE || (JAC && FANR == 9 && !STAGE && !LDSG), "PIPE: the direct Jacobian walk");
   extern __shared__ double srec[];  // LDSG: [cnt][RW] = x, y, dofs, aux0, aux1
-  const int blk = row_block(L, blockIdx.x, gridDim.x);
-  const int row0 = blk * blockDim.x + threadIdx.x;
-  const bool live = row0 < L.n_owned;
-  if (!LDSG && !live) return;
-  // the row's own loads first (LDSG: they are in flight while the workgroup stages the
-  // neighbour records, instead of after its barrier)
-  const int row = live ? row0 : 0;
-  const int chunk = row / kRows, lane = row % kRows;
-  const int off = L.chunk_off[chunk];
-  const uint64_t meta = L.rowmeta[row];
-  const int len = int(meta & 63);
-  const bool closed = (meta >> 6) & 1;
-  const unsigned brk = unsigned(meta >> 8);  // fan-break bits, bit s: no element after slot s
-  double *__restrict__ vc = a.vals + size_t(off) * NK;  // chunk base (k-form), see vin()
-
-  int cj[NS];  // the fan's columns (LDSG: their positions in the staged list)
-  if constexpr (LDSG) {
-    const uint16_t *__restrict__ lix = L.lidx + off + lane;
+  __shared__ uint32_t pfb[PIPE ? 4 * kPipeDw * kRows : 1];  // PIPE: the waves' prefetch regions
+  // PIPE, wave-uniform: the 256-row blocks of this and the next two tiles (-1: none), this and
+  // the next tile's chunk offset and the next one's slot count
+  const int ntiles = (L.n_owned + 255) / 256, G = gridDim.x;
+  const int wv = PIPE ? __builtin_amdgcn_readfirstlane(int(threadIdx.x) / kRows) : 0;
+  const int ln = int(threadIdx.x) % kRows;
+  uint32_t *const pw = pfb + (PIPE ? wv * kPipeDw * kRows : 0);
+  int tile = blockIdx.x, b0 = -1, b1 = -1, b2 = -1, o0 = 0, o1 = 0, c1 = 0;
+  auto tile_blk = [&](int t) { return t < ntiles ? row_block_const(L, t, ntiles) : -1; };
+  // chunk of the wave's rows in block b (-1: b is no block, or the wave's rows are past the end)
+  auto wave_chunk = [&](int b) {
+    return (b >= 0 && b * 256 + wv * kRows < L.n_owned) ? b * 4 + wv : -1;
+  };
+  auto prefetch = [&](int b, int off, int clen) {  // all lanes; rows past the end read row n - 1
+    if (wave_chunk(b) < 0) return;
+    const int r0 = b * 256 + wv * kRows;
+    const int *cix = L.colidx + off + ln;
 #pragma unroll
-    for (int k = 1; k < NS; k++) {  // past the fan: entry 0 (slot 0's own row is not staged)
-      const int t = lix[(k < len ? k : 0) * kRows];
-      cj[k] = k < len ? t : 0;
+    for (int k = 1; k < NS; k++)  // past the chunk's slots: slot 0 (padding slots hold the row)
+      lds_dma4(cix + (k < clen ? k : 0) * kRows, pw + (k - 1) * kRows);
+    const uint32_t *m =
+        reinterpret_cast<const uint32_t *>(L.rowmeta + min(r0 + ln, L.n_owned - 1));
+    lds_dma4(m, pw + 8 * kRows);
+    lds_dma4(m + 1, pw + 9 * kRows);
+    lds_dma4(reinterpret_cast<const uint32_t *>(a.rowflag + r0) + (ln >> 2), pw + 10 * kRows);
+  };
+  if constexpr (PIPE) {
+    if (tile >= ntiles) return;
+    b0 = tile_blk(tile);
+    b1 = tile_blk(tile + G);
+    b2 = tile_blk(tile + 2 * G);
+    int c0 = 0;
+    if (wave_chunk(b0) >= 0) {
+      o0 = const_ld(L.chunk_off, wave_chunk(b0));
+      c0 = const_ld(L.chunk_len, wave_chunk(b0));
     }
-  } else {
-    const int *__restrict__ cix = L.colidx + off + lane;
-#pragma unroll
-    for (int k = 1; k < NS; k++) cj[k] = cix[(k < len ? k : 0) * kRows];  // past the fan: the row
+    if (wave_chunk(b1) >= 0) {
+      o1 = const_ld(L.chunk_off, wave_chunk(b1));
+      c1 = const_ld(L.chunk_len, wave_chunk(b1));
+    }
+    prefetch(b0, o0, c0);
   }
-  const double2 pi2 = reinterpret_cast<const double2 *>(L.xy)[row];
-  double ui[NF];
-  load_nf<NF>(a.x, size_t(row), ui);
-  double ai = 0, aq = 0;
-  if constexpr (AUX0) ai = a.aux0[row];
-  if constexpr (AUX1) aq = a.aux1[row];
-  if constexpr (OP == OP_PB) pb_fifth(ui[0], ai, aq);  // element(): e^{u/5}, e^{-u/5} per vertex
-  if constexpr (LDSG) {
-    const int u0 = L.uptr[blk], cnt = L.uown[blk];  // the fan neighbours (own rows come after)
-    // up to ASM_SU list entries per thread: their list loads, then their gathers, then the LDS
-    // stores (two round trips, not two per entry; ~1,000 distinct columns per block at config 3)
-    constexpr int kSU = ASM_SU;
-    int jj[kSU];
+  int o2 = 0, c2 = 0, b3 = -1;  // PIPE: the scalars of tile + 2 G, tile + 3 G, loaded mid-tile
+  const auto advance = [&]() {   // PIPE: on to the workgroup's next tile
+    tile += G;
+    b0 = b1, o0 = o1;
+    b1 = b2, o1 = o2, c1 = c2;
+    b2 = b3;
+    return b0 >= 0;
+  };
+  do {
+    const int blk = PIPE ? b0 : row_block(L, blockIdx.x, gridDim.x);
+    const int row0 = blk * blockDim.x + threadIdx.x;
+    const bool live = row0 < L.n_owned;
+    if (!PIPE && !LDSG && !live) return;
+    // the row's own loads first (LDSG: they are in flight while the workgroup stages the
+    // neighbour records, instead of after its barrier)
+    const int row = live ? row0 : 0;
+    const int chunk = row / kRows, lane = row % kRows;
+    int cj[NS];  // the fan's columns (LDSG: their positions in the staged list)
+    uint64_t meta_pf = 0;
+    unsigned fl_pf = 0;
+    if constexpr (PIPE) {
+      // The compiler orders neither the DMA loads before these LDS reads nor the reads before the
+      // next DMA loads (seen in the ISA), so both waits are explicit: the tile's DMA loads have
+      // landed (vmcnt counts in issue order: so have the previous tile's stores) ...
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-    for (int u = 0; u < kSU; u++) {
-      const int k = int(threadIdx.x) + u * 256;
-      jj[u] = k < cnt ? L.ulist[u0 + k] : -1;
-    }
-    double t[kSU][RW];
-#pragma unroll
-    for (int u = 0; u < kSU; u++)
-      if (jj[u] >= 0) {
-        const double2 p = reinterpret_cast<const double2 *>(L.xy)[jj[u]];
-        t[u][0] = p.x;
-        t[u][1] = p.y;
-        double uu[NF];
-        load_nf<NF>(a.x, size_t(jj[u]), uu);
-#pragma unroll
-        for (int f = 0; f < NF; f++) t[u][2 + f] = uu[f];
-        if constexpr (AUX0) t[u][2 + NF] = a.aux0[jj[u]];
-        if constexpr (AUX1) t[u][3 + NF] = a.aux1[jj[u]];
+      for (int k = 1; k < NS; k++) cj[k] = int(pw[(k - 1) * kRows + ln]);
+      meta_pf = uint64_t(pw[8 * kRows + ln]) | (uint64_t(pw[9 * kRows + ln]) << 32);
+      fl_pf = (pw[10 * kRows + ln] >> (8 * (ln & 3))) & 0xffu;
+      // ... and the region is read out before the next tile's loads may write it; then the scalars
+      // of the tile after that
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      prefetch(b1, o1, c1);
+      o2 = c2 = 0;
+      if (wave_chunk(b2) >= 0) {
+        o2 = const_ld(L.chunk_off, wave_chunk(b2));
+        c2 = const_ld(L.chunk_len, wave_chunk(b2));
       }
-#pragma unroll
-    for (int u = 0; u < kSU; u++)
-      if (jj[u] >= 0)
-#pragma unroll
-        for (int w = 0; w < RW; w++) srec[size_t(int(threadIdx.x) + u * 256) * RW + w] = t[u][w];
-    for (int k = int(threadIdx.x) + kSU * 256; k < cnt; k += blockDim.x) {
-      const int j = L.ulist[u0 + k];
-      const double2 p = reinterpret_cast<const double2 *>(L.xy)[j];
-      double u[NF];
-      load_nf<NF>(a.x, size_t(j), u);
-      double *r = srec + size_t(k) * RW;
-      r[0] = p.x;
-      r[1] = p.y;
-#pragma unroll
-      for (int f = 0; f < NF; f++) r[2 + f] = u[f];
-      if constexpr (AUX0) r[2 + NF] = a.aux0[j];
-      if constexpr (AUX1) r[3 + NF] = a.aux1[j];
+      b3 = tile_blk(tile + 3 * G);
+      if (!live) continue;
     }
-    __syncthreads();
-    if (!live) return;
-  }
-  double2 pn[NS];
-  double un[NS][NF], a0[NS], a1[NS];
-  auto gather = [&](int k) {
+    const int off = PIPE ? o0 : L.chunk_off[chunk];
+    const uint64_t meta = PIPE ? meta_pf : L.rowmeta[row];
+    const int len = int(meta & 63);
+    const bool closed = (meta >> 6) & 1;
+    const unsigned brk = unsigned(meta >> 8);  // fan-break bits, bit s: no element after slot s
+    double *__restrict__ vc = a.vals + size_t(off) * NK;  // chunk base (k-form), see vin()
+
+    if constexpr (PIPE) {
+      // cj came from the prefetch region above
+    } else if constexpr (LDSG) {
+      const uint16_t *__restrict__ lix = L.lidx + off + lane;
+#pragma unroll
+      for (int k = 1; k < NS; k++) {  // past the fan: entry 0 (slot 0's own row is not staged)
+        const int t = lix[(k < len ? k : 0) * kRows];
+        cj[k] = k < len ? t : 0;
+      }
+    } else {
+      const int *__restrict__ cix = L.colidx + off + lane;
+#pragma unroll
+      // past the fan: the row
+      for (int k = 1; k < NS; k++) cj[k] = cix[(k < len ? k : 0) * kRows];
+    }
+    const double2 pi2 = reinterpret_cast<const double2 *>(L.xy)[row];
+    double ui[NF];
+    load_nf<NF>(a.x, size_t(row), ui);
+    double ai = 0, aq = 0;
+    if constexpr (AUX0) ai = a.aux0[row];
+    if constexpr (AUX1) aq = a.aux1[row];
+    if constexpr (OP == OP_PB) pb_fifth(ui[0], ai, aq);  // element(): e^{u/5}, e^{-u/5} per vertex
     if constexpr (LDSG) {
-      const double *r = srec + size_t(cj[k]) * RW;
-      pn[k] = make_double2(r[0], r[1]);
+      const int u0 = L.uptr[blk], cnt = L.uown[blk];  // the fan neighbours (own rows come after)
+      // up to ASM_SU list entries per thread: their list loads, then their gathers, then the LDS
+      // stores (two round trips, not two per entry; ~1,000 distinct columns per block at config 3)
+      constexpr int kSU = ASM_SU;
+      int jj[kSU];
 #pragma unroll
-      for (int f = 0; f < NF; f++) un[k][f] = r[2 + f];
-      a0[k] = AUX0 ? r[2 + NF] : 0.0;
-      a1[k] = AUX1 ? r[3 + NF] : 0.0;
-    } else {
-      pn[k] = reinterpret_cast<const double2 *>(L.xy)[cj[k]];
-      load_nf<NF>(a.x, size_t(cj[k]), un[k]);
-      a0[k] = AUX0 ? a.aux0[cj[k]] : 0.0;
-      a1[k] = AUX1 ? a.aux1[cj[k]] : 0.0;
-    }
-  };
-#pragma unroll
-  for (int k = 1; k < SPLIT; k++) gather(k);
-  // PB: slot k's e^{u/5} goes to a0[k] / a1[k] when element k - 1 needs it (slot 1: up front)
-  if constexpr (OP == OP_PB) pb_fifth(un[1][0], a0[1], a1[1]);
-
-  double R[NF], D[NK], P[NK], F[NK];
-#pragma unroll
-  for (int f = 0; f < NF; f++) R[f] = 0;
-#pragma unroll
-  for (int v = 0; v < NK; v++) D[v] = P[v] = F[v] = 0;
-  // STAGE: blocks finished before the second-half gathers are issued (slots 1 .. SPLIT-3) wait
-  // in LDS and go out right after those gathers: vmcnt retires loads and stores in issue order,
-  // so a gather issued behind a store also waits for the store (A/B knob PNP_ASM_GA=6)
-  constexpr int NSTG = (STAGE && JAC && SPLIT < NS && SPLIT > 3) ? SPLIT - 3 : 0;
-  __shared__ double stg[NSTG > 0 ? NSTG * NK * 256 : 1];
-  unsigned staged = 0;
-  auto put = [&](int s, const double *Kc) {
-    if (NSTG > 0 && s <= NSTG) {
-#pragma unroll
-      for (int v = 0; v < NK; v++) stg[((s - 1) * NK + v) * 256 + threadIdx.x] = Kc[v];
-      staged |= 1u << s;
-    } else {
-      store_block<OP, KC>(vc, lane, s, Kc);
-    }
-  };
-#pragma unroll
-  for (int s = 1; s < NS; s++) {
-    if (SPLIT < NS && s == (SPLIT > 2 ? SPLIT - 2 : 1)) {
-#pragma unroll
-      for (int k = SPLIT; k < NS; k++) gather(k);
-      if constexpr (NSTG > 0) {
-#pragma unroll
-        for (int q = 1; q <= NSTG; q++)
-          if ((staged >> q) & 1) {
-            double K[NK];
-#pragma unroll
-            for (int v = 0; v < NK; v++) K[v] = stg[((q - 1) * NK + v) * 256 + threadIdx.x];
-            store_block<OP, KC>(vc, lane, q, K);
-          }
+      for (int u = 0; u < kSU; u++) {
+        const int k = int(threadIdx.x) + u * 256;
+        jj[u] = k < cnt ? L.ulist[u0 + k] : -1;
       }
-    }
-    if (s < len) {
-      const bool has_next = s + 1 < len;
-      const int sn = (s + 1 < NS) ? s + 1 : 1;  // static slot of v_{s+1}
-      const bool elem = (has_next || closed) && !((brk >> s) & 1);
-      if constexpr (OP == OP_PB)
-        if (has_next) pb_fifth(un[sn][0], a0[sn], a1[sn]);
-      if (elem) {
-        // v_t = v_{s+1}, or v_1 when a closed fan wraps
-        const double2 pt = has_next ? pn[sn] : pn[1];
-        double ut[NF];
+      double t[kSU][RW];
 #pragma unroll
-        for (int f = 0; f < NF; f++) ut[f] = has_next ? un[sn][f] : un[1][f];
-        const double at0 = has_next ? a0[sn] : a0[1], at1 = has_next ? a1[sn] : a1[1];
-        Geo G;
-        geometry(pi2.x, pi2.y, pn[s].x, pn[s].y, pt.x, pt.y, G);
-        double Ct[NK];
+      for (int u = 0; u < kSU; u++)
+        if (jj[u] >= 0) {
+          const double2 p = reinterpret_cast<const double2 *>(L.xy)[jj[u]];
+          t[u][0] = p.x;
+          t[u][1] = p.y;
+          double uu[NF];
+          load_nf<NF>(a.x, size_t(jj[u]), uu);
 #pragma unroll
-        for (int v = 0; v < NK; v++) Ct[v] = 0;
-        element<OP, JAC, KC>(a, G, pi2.y, pn[s].y, pt.y, ui, un[s], ut, ai, a0[s], at0, aq,
-                             a1[s], at1, R, D, P, Ct);
-        if constexpr (JAC) {
-          if (s == 1 && closed) {
-#pragma unroll
-            for (int v = 0; v < NK; v++) F[v] = P[v];
-          } else {
-            put(s, P);
-          }
-#pragma unroll
-          for (int v = 0; v < NK; v++) P[v] = Ct[v];
+          for (int f = 0; f < NF; f++) t[u][2 + f] = uu[f];
+          if constexpr (AUX0) t[u][2 + NF] = a.aux0[jj[u]];
+          if constexpr (AUX1) t[u][3 + NF] = a.aux1[jj[u]];
         }
-      } else if constexpr (JAC) {
-        put(s, P);
 #pragma unroll
-        for (int v = 0; v < NK; v++) P[v] = 0;
+      for (int u = 0; u < kSU; u++)
+        if (jj[u] >= 0)
+#pragma unroll
+          for (int w = 0; w < RW; w++) srec[size_t(int(threadIdx.x) + u * 256) * RW + w] = t[u][w];
+      for (int k = int(threadIdx.x) + kSU * 256; k < cnt; k += blockDim.x) {
+        const int j = L.ulist[u0 + k];
+        const double2 p = reinterpret_cast<const double2 *>(L.xy)[j];
+        double u[NF];
+        load_nf<NF>(a.x, size_t(j), u);
+        double *r = srec + size_t(k) * RW;
+        r[0] = p.x;
+        r[1] = p.y;
+#pragma unroll
+        for (int f = 0; f < NF; f++) r[2 + f] = u[f];
+        if constexpr (AUX0) r[2 + NF] = a.aux0[j];
+        if constexpr (AUX1) r[3 + NF] = a.aux1[j];
+      }
+      __syncthreads();
+      if (!live) return;
+    }
+    double2 pn[NS];
+    double un[NS][NF], a0[NS], a1[NS];
+    auto gather = [&](int k) {
+      if constexpr (LDSG) {
+        const double *r = srec + size_t(cj[k]) * RW;
+        pn[k] = make_double2(r[0], r[1]);
+#pragma unroll
+        for (int f = 0; f < NF; f++) un[k][f] = r[2 + f];
+        a0[k] = AUX0 ? r[2 + NF] : 0.0;
+        a1[k] = AUX1 ? r[3 + NF] : 0.0;
+      } else {
+        pn[k] = reinterpret_cast<const double2 *>(L.xy)[cj[k]];
+        load_nf<NF>(a.x, size_t(cj[k]), un[k]);
+        a0[k] = AUX0 ? a.aux0[cj[k]] : 0.0;
+        a1[k] = AUX1 ? a.aux1[cj[k]] : 0.0;
+      }
+    };
+#pragma unroll
+    for (int k = 1; k < SPLIT; k++) gather(k);
+    // PB: slot k's e^{u/5} goes to a0[k] / a1[k] when element k - 1 needs it (slot 1: up front)
+    if constexpr (OP == OP_PB) pb_fifth(un[1][0], a0[1], a1[1]);
+
+    double R[NF], D[NK], P[NK], F[NK];
+#pragma unroll
+    for (int f = 0; f < NF; f++) R[f] = 0;
+#pragma unroll
+    for (int v = 0; v < NK; v++) D[v] = P[v] = F[v] = 0;
+    // STAGE: blocks finished before the second-half gathers are issued (slots 1 .. SPLIT-3) wait
+    // in LDS and go out right after those gathers: vmcnt retires loads and stores in issue order,
+    // so a gather issued behind a store also waits for the store (A/B knob PNP_ASM_GA=6)
+    constexpr int NSTG = (STAGE && JAC && SPLIT < NS && SPLIT > 3) ? SPLIT - 3 : 0;
+    __shared__ double stg[NSTG > 0 ? NSTG * NK * 256 : 1];
+    unsigned staged = 0;
+    auto put = [&](int s, const double *Kc) {
+      if (NSTG > 0 && s <= NSTG) {
+#pragma unroll
+        for (int v = 0; v < NK; v++) stg[((s - 1) * NK + v) * 256 + threadIdx.x] = Kc[v];
+        staged |= 1u << s;
+      } else {
+        store_block<OP, KC>(vc, lane, s, Kc);
+      }
+    };
+#pragma unroll
+    for (int s = 1; s < NS; s++) {
+      if (SPLIT < NS && s == (SPLIT > 2 ? SPLIT - 2 : 1)) {
+#pragma unroll
+        for (int k = SPLIT; k < NS; k++) gather(k);
+        if constexpr (NSTG > 0) {
+#pragma unroll
+          for (int q = 1; q <= NSTG; q++)
+            if ((staged >> q) & 1) {
+              double K[NK];
+#pragma unroll
+              for (int v = 0; v < NK; v++) K[v] = stg[((q - 1) * NK + v) * 256 + threadIdx.x];
+              store_block<OP, KC>(vc, lane, q, K);
+            }
+        }
+      }
+      if (s < len) {
+        const bool has_next = s + 1 < len;
+        const int sn = (s + 1 < NS) ? s + 1 : 1;  // static slot of v_{s+1}
+        const bool elem = (has_next || closed) && !((brk >> s) & 1);
+        if constexpr (OP == OP_PB)
+          if (has_next) pb_fifth(un[sn][0], a0[sn], a1[sn]);
+        if (elem) {
+          // v_t = v_{s+1}, or v_1 when a closed fan wraps
+          const double2 pt = has_next ? pn[sn] : pn[1];
+          double ut[NF];
+#pragma unroll
+          for (int f = 0; f < NF; f++) ut[f] = has_next ? un[sn][f] : un[1][f];
+          const double at0 = has_next ? a0[sn] : a0[1], at1 = has_next ? a1[sn] : a1[1];
+          Geo G;
+          geometry(pi2.x, pi2.y, pn[s].x, pn[s].y, pt.x, pt.y, G);
+          double Ct[NK];
+#pragma unroll
+          for (int v = 0; v < NK; v++) Ct[v] = 0;
+          element<OP, JAC, KC>(a, G, pi2.y, pn[s].y, pt.y, ui, un[s], ut, ai, a0[s], at0, aq,
+                               a1[s], at1, R, D, P, Ct);
+          if constexpr (JAC) {
+            if (s == 1 && closed) {
+#pragma unroll
+              for (int v = 0; v < NK; v++) F[v] = P[v];
+            } else {
+              put(s, P);
+            }
+#pragma unroll
+            for (int v = 0; v < NK; v++) P[v] = Ct[v];
+          }
+        } else if constexpr (JAC) {
+          put(s, P);
+#pragma unroll
+          for (int v = 0; v < NK; v++) P[v] = 0;
+        }
       }
     }
-  }
-  if constexpr (JAC) {
-    if (closed) {
+    if constexpr (JAC) {
+      if (closed) {
 #pragma unroll
-      for (int v = 0; v < NK; v++) F[v] += P[v];
-      store_block<OP, KC>(vc, lane, 1, F);
+        for (int v = 0; v < NK; v++) F[v] += P[v];
+        store_block<OP, KC>(vc, lane, 1, F);
+      }
+      store_block<OP, KC>(vc, lane, 0, D);
     }
-    store_block<OP, KC>(vc, lane, 0, D);
-  }
-#pragma unroll
-  for (int f = 0; f < NF; f++) {
-    const size_t q = size_t(row) * NF + f;
-    const double rv = R[f] + a.cvec[q];
-    a.r[q] = a.dmask[q] != 0 ? 0.0 : rv;
-  }
+    residual_tail<NF>(a, row, PIPE ? fl_pf : unsigned(a.rowflag[row]), R);
+  } while (PIPE && advance());
 }
 
 // cvec[row] -= M(x_old)[row]: PnpTOperator (tau * (c+ + c-) into the c+ row, Q2) or the
@@ -532,8 +652,41 @@ hipError_t launch_ion_flux(int ns, const int4 *seg, const double *xy, const doub
 // (hipExtLaunchKernelGGL), so the library's timers see the kernel's own duration -- an event pair
 // recorded around the launch adds the dispatch of two markers (~5 us at config 3 in situ, against
 // the kernel trace: 75.7 vs 69.6 us, gpurun_out r6final1 / profiles/r06/asm_regimes_config3.json)
+// PNP_ASM_PIPE's default: off.  At config 3 the pipelined walk measured 44.1 us per warm launch
+// against 39.6 for the direct walk (parent commit: 42.4), at every grid from one tile per
+// workgroup to the resident grid (profiles/asm_pipe/)
+constexpr bool kAsmPipeDefault = false;
+
+// The pipelined walk's launch (operators with constant planes: OP_PNP).  Grid: the workgroups
+// resident at once (occupancy x CUs) rounded down to a multiple of 8, at most one per tile, at
+// most cap (> 0).  Returns 1 when it launched.
+template <int OP>
+static int launch_pipe(const DevLayout &L, const AsmArgs &a, int cap, hipStream_t s, hipEvent_t t0,
+                       hipEvent_t t1) {
+  if constexpr (asm_kc<OP>()) {
+    const auto kern = k_assemble_ga<OP, 1, 3, 9, 6, 0, 0, 1, 1>;
+    static const int resident = [&] {
+      int dev = 0, cus = 0, per_cu = 0;
+      if (hipGetDevice(&dev) != hipSuccess ||
+          hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 256, 0) != hipSuccess)
+        return 0;
+      return per_cu * cus;
+    }();
+    const int ntiles = (L.n_owned + 255) / 256;
+    int g = resident >= 8 ? resident / 8 * 8 : 8;
+    if (g > ntiles) g = ntiles;
+    if (cap > 0 && g > cap) g = cap;
+    hipExtLaunchKernelGGL(kern, dim3(g), dim3(256), 0, s, t0, t1, 0, L, a);
+    return 1;
+  } else {
+    return 0;
+  }
+}
+
 hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, hipEvent_t t0,
-                           hipEvent_t t1) {
+                           hipEvent_t t1, int *pipelined) {
+  if (pipelined) *pipelined = 0;
   if (L.n_owned == 0) return hipSuccess;
   dim3 grid((L.n_owned + 255) / 256), block(256);
   // occupancy variant (A/B knob, PNP_ASM_WAVES=3|4): 4 waves/SIMD caps the fused PNP kernel at
@@ -586,6 +739,19 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
            (lds_env < 0 && (size_t(L.n_owned) * 7 * size_t(nk) * 8 > (size_t(512) << 20) ||
                             (cold_hint && a.cold)));
   };
+  // The persistent, prefetching walk (k_assemble_ga<..., PIPE = 1>) in place of the direct
+  // constant-planes walk: PNP_ASM_PIPE=1 (0, the default: the direct walk; read once per
+  // process).  The cold / in-situ launches keep the LDS-staged walk.  PNP_ASM_PIPE_GRID=n caps
+  // its grid at n workgroups (A/B and test knob: any n >= 1 is correct).
+  static const bool pipe_on = [] {
+    const char *e = getenv("PNP_ASM_PIPE");
+    return e ? atoi(e) != 0 : kAsmPipeDefault;
+  }();
+  static const int pipe_cap = [] {
+    const char *e = getenv("PNP_ASM_PIPE_GRID");
+    return (e && atoi(e) >= 1) ? atoi(e) : 0;
+  }();
+  int piped = 0;
 #define PNP_ASM_CASE(OPK)                                                          \
   case OPK:                                                                        \
     if (!fanr && a.jac)                                                            \
@@ -611,6 +777,8 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
              size_t(L.unmax) * asm_lds_rec<OPK>() * 8 <= 53 * 1024)                    \
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 1, asm_kc<OPK>()>), grid,  \
                          block, size_t(L.unmax) * asm_lds_rec<OPK>() * 8, s, t0, t1, 0, L, a); \
+    else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst && pipe_on)         \
+      piped = launch_pipe<OPK>(L, a, pipe_cap, s, t0, t1);                         \
     else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst)                    \
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 0, asm_kc<OPK>()>), grid,  \
                          block, 0, s, t0, t1, 0, L, a);                             \
@@ -642,6 +810,7 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
     return hipErrorInvalidValue;
   }
 #undef PNP_ASM_CASE
+  if (pipelined) *pipelined = piped;
   return hipGetLastError();
 }
 

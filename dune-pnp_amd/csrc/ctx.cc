@@ -303,6 +303,9 @@ struct pnp_ctx {
   std::vector<int> fseg_group;
   DBuf<double> fluxout, fluxx, fluxred;
   DBuf<uint8_t> dmask;
+  // AsmArgs::rowflag of the operator set now: a byte per owned row, whole SELL chunks (padding 0)
+  DBuf<uint8_t> rowflag;
+  std::vector<uint8_t> hrowflag;  // its owned rows on the host (pnp_asm_row_flags)
   DBuf<double> cvec, aux0, aux1;
   bool assembled = false;
   bool after_solve = false;  // a linear solve ran since the last Jacobian assembly (AsmArgs::cold)
@@ -334,7 +337,8 @@ struct pnp_ctx {
     return (e && std::atoi(e) == 0) ? 0 : 1;
   }();
   bool vals_const_valid = false;
-  long long asm_full = 0, asm_reused = 0;  // pnp_asm_info
+  // pnp_asm_info; asm_piped: launches of the persistent, prefetching walk (PNP_ASM_PIPE)
+  long long asm_full = 0, asm_reused = 0, asm_piped = 0;
   bool asm_kconst() const {
     return asm_reuse_opt && vals_const_valid && degree == 1 && !fd_mode && kind == PNP_OP_PNP;
   }
@@ -891,10 +895,11 @@ struct pnp_ctx {
       t0 = tb(T_ASM);
     }
     hipError_t e;
+    int piped = 0;
     if (degree > 1)
       e = pnp::launch_pk_assemble(dl, aa, pkd, jac ? (fd_mode ? 2 : 1) : 0, stream);
     else
-      e = pnp::launch_assemble(dl, aa, stream, t1 ? t0 : nullptr, t1);
+      e = pnp::launch_assemble(dl, aa, stream, t1 ? t0 : nullptr, t1, &piped);
     if (e == hipSuccess && jac && fd_mode && degree == 1)
       e = pnp::launch_fd_jacobian(dl, aa, nf, pat, fd_ne, fd_etri.p, fd_rptr.p, fd_cdata.p,
                                   fd_jel.p, stream);
@@ -903,6 +908,7 @@ struct pnp_ctx {
       return hipfail(e, "assemble");
     }
     if (jac && !mf) asm_wrote(aa.kconst != 0, degree == 1 && !fd_mode);
+    asm_piped += piped;
     if (t1) {
       ev_pending[T_ASM].push_back({t0, t1});
       t_n[T_ASM]++;
@@ -955,12 +961,14 @@ struct pnp_ctx {
     fa.cold = after_solve ? 1 : 0;
     fa.kconst = asm_kconst() ? 1 : 0;
     hipEvent_t t0 = tb(T_ASM);
-    e = pnp::launch_assemble(dl, fa, stream);
+    int piped = 0;
+    e = pnp::launch_assemble(dl, fa, stream, nullptr, nullptr, &piped);
     if (e != hipSuccess) {
       vals_const_valid = false;
       return hipfail(e, "assemble at the linearisation point");
     }
     asm_wrote(fa.kconst != 0, true);
+    asm_piped += piped;
     te(T_ASM, t0);
     vals_stale = false;
     value_assemblies++;
@@ -3675,6 +3683,7 @@ extern "C" int pnp_create_pk(const pnp_mesh *mesh, const pnp_params *params, int
                "partials2")) ||
       (rc = al(c->S, 2, "scalars")) || (rc = al(c->redmw, pnp::kRedMwDoubles, "reduce ticket")) ||
       (rc = al(c->dmask, 3 * size_t(L.n_owned), "dmask")) ||
+      (rc = al(c->rowflag, size_t(L.nchunks + 1) * pnp::kRows, "row flags")) ||
       (rc = al(c->cvec, 3 * size_t(L.n_owned), "cvec")) || (rc = al(c->aux0, nloc, "aux0")) ||
       (rc = al(c->aux1, nloc, "aux1"))) {
     g_err = c->err;
@@ -3890,6 +3899,27 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
       if (a->c_extra) lload[size_t(i) * nf + f] += a->c_extra[size_t(f) * m.nv + L.l2g[i]];
     }
   CK(hipMemcpy(c->dmask.p, lmask.data(), lmask.size(), hipMemcpyHostToDevice), "dmask");
+  {  // the P1 assembly's flag byte per row: its mask bits, and whether its load is to be read --
+     // any entry that is not bitwise +0.0 (-0.0 too); implicit Euler: every row, the device mass
+     // kernel rewrites cvec below
+    std::vector<uint8_t> flag(c->rowflag.n, 0);
+    for (int i = 0; i < L.n_owned; i++) {
+      unsigned fl = ie ? pnp::kRowFlagLoad : 0;
+      for (int f = 0; f < nf; f++) {
+        if (lmask[size_t(i) * nf + f]) fl |= 1u << f;
+        uint64_t bits;
+        std::memcpy(&bits, &lload[size_t(i) * nf + f], sizeof bits);
+        if (bits) fl |= pnp::kRowFlagLoad;
+        if (a->c_extra) {  // a caller's entry flags its row whatever the sum came to (-0.0 too)
+          std::memcpy(&bits, &a->c_extra[size_t(f) * m.nv + L.l2g[i]], sizeof bits);
+          if (bits) fl |= pnp::kRowFlagLoad;
+        }
+      }
+      flag[i] = uint8_t(fl);
+    }
+    CK(hipMemcpy(c->rowflag.p, flag.data(), flag.size(), hipMemcpyHostToDevice), "row flags");
+    c->hrowflag.assign(flag.begin(), flag.begin() + L.n_owned);
+  }
   // the reference-order mode's copies (external layout, global vertex order)
   c->seq_op_valid = false;
   c->seq_dt = a->dt;
@@ -3948,6 +3978,7 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   aa.aux1 = c->aux1.p;
   aa.cvec = c->cvec.p;
   aa.dmask = c->dmask.p;
+  aa.rowflag = c->rowflag.p;
   aa.vals = c->vals.p;
   return PNP_OK;
 }
@@ -4429,10 +4460,20 @@ extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_ass
   return PNP_OK;
 }
 
-extern "C" int pnp_asm_info(pnp_ctx *c, int64_t *full, int64_t *reused) {
+extern "C" int pnp_asm_row_flags(pnp_ctx *c, uint8_t *flags) {
+  if (!c || !flags) return PNP_E_ARG;
+  if (c->kind < 0) return c->fail(PNP_E_STATE, "no operator set (pnp_set_operator)");
+  if (c->degree > 1) return c->fail(PNP_E_STATE, "row flags: P1 contexts only");
+  std::memset(flags, 0xff, size_t(c->mesh.nv));
+  for (int i = 0; i < c->L.n_owned; i++) flags[c->L.l2g[i]] = c->hrowflag[i];
+  return PNP_OK;
+}
+
+extern "C" int pnp_asm_info(pnp_ctx *c, int64_t *full, int64_t *reused, int64_t *pipelined) {
   if (!c) return PNP_E_ARG;
   if (full) *full = c->asm_full;
   if (reused) *reused = c->asm_reused;
+  if (pipelined) *pipelined = c->asm_piped;
   return PNP_OK;
 }
 

@@ -282,6 +282,10 @@ __device__ __forceinline__ unsigned row_mask(const DevLayout &L, int row) {
   return dm;
 }
 
+// AsmArgs::rowflag: bits 0 .. NF-1 = the row's Dirichlet mask; kRowFlagLoad = some cvec entry of
+// the row is not bitwise +0.0 (the others add a literal +0.0 and do not load cvec)
+constexpr unsigned kRowFlagMask = 7, kRowFlagLoad = 8;
+
 struct AsmArgs {
   int kind;
   int jac;               // 1: residual + Jacobian, 0: residual only
@@ -291,7 +295,10 @@ struct AsmArgs {
   const double *aux0;    // DIFF: phi [n_local]; POISSON: cp [n_local]
   const double *aux1;    // POISSON: cm [n_local]
   const double *cvec;    // constant part of the residual [n_owned * NF] (Neumann load, old mass)
-  const uint8_t *dmask;  // Dirichlet mask [n_owned * NF]
+  const uint8_t *dmask;  // Dirichlet mask [n_owned * NF] (P_k assembly, matrix-free application)
+  // one byte per owned row, padded to whole SELL chunks (kRowFlag*): what the P1 assembly's
+  // residual tail reads in place of the row's mask bytes and, on most rows, of its cvec entries
+  const uint8_t *rowflag;
   double *r;             // [n_owned * NF]
   double *vals;          // SELL values
   int cold;              // 1: the launch follows a linear solve (Newton's Jacobian): its inputs are
@@ -315,8 +322,11 @@ struct Scalars {
 };
 
 // ---- launchers (return hipError_t of the launch) ----------------------------------------------
+// *pipelined (may be null): set to 1 when the launch was the persistent, prefetching walk
+// (k_assemble_ga<..., PIPE = 1>, PNP_ASM_PIPE), to 0 otherwise
 hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s,
-                           hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr);
+                           hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr,
+                           int *pipelined = nullptr);
 // old-time mass M(x_old) (PnpTOperator / DiffusionTOperator) subtracted into cvec
 hipError_t launch_ion_flux(int ns, const int4 *seg, const double *xy, const double *x, int cyl,
                            double pi, double *out, hipStream_t s);

@@ -37,6 +37,10 @@ METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES = 0, 1, 2, 3
  OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
  OPT_GMRES_RESTART, OPT_MATRIX_FREE, OPT_ASM_REUSE_CONST) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11,
                                                              12, 13)
+# environment variables of the library, read once per process (include/pnp_capi.h, pnp_asm_info):
+# the persistent, prefetching PNP assembly walk on / off, and a cap on its grid (A/B, tests)
+ASM_PIPE_ENV, ASM_PIPE_GRID_ENV = "PNP_ASM_PIPE", "PNP_ASM_PIPE_GRID"
+ROW_FLAG_LOAD = 8  # PNP_ROW_FLAG_LOAD
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
 PREC_BY_NAME = {"none": PREC_NONE, "nonprec": PREC_NONE, "ssor": PREC_SSOR, "ilu0": PREC_ILU0,
@@ -801,10 +805,18 @@ class Context:
     def asm_info(self):
         """Jacobian assemblies since the context was created that wrote every plane of the SELL
         values, and PNP assemblies that kept the stored state-independent planes
-        (OPT_ASM_REUSE_CONST)."""
-        f, r = C.c_int64(), C.c_int64()
-        self._ck(lib().pnp_asm_info(self.h, C.byref(f), C.byref(r)))
-        return {"full": f.value, "reused": r.value}
+        (OPT_ASM_REUSE_CONST); "pipelined": those of the latter launched as the persistent,
+        prefetching walk (ASM_PIPE_ENV, capped by ASM_PIPE_GRID_ENV)."""
+        f, r, p = C.c_int64(), C.c_int64(), C.c_int64()
+        self._ck(lib().pnp_asm_info(self.h, C.byref(f), C.byref(r), C.byref(p)))
+        return {"full": f.value, "reused": r.value, "pipelined": p.value}
+
+    def asm_row_flags(self):
+        """pnp_asm_row_flags: the assembly's flag byte per vertex of the operator set now (bits
+        0 .. nf-1 the Dirichlet mask, ROW_FLAG_LOAD: the row's constant load is read)."""
+        out = np.zeros(self.mesh.nv, dtype=np.uint8)
+        self._ck(lib().pnp_asm_row_flags(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def probe_slot_stores(self, tile_elems=256, reps=20):
         """pnp_probe_slot_stores (P_k contexts): the SELL slot stores of one Jacobian in SELL,

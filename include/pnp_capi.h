@@ -493,8 +493,19 @@ enum {
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
 /* Jacobian assemblies that wrote the SELL values, since the context was created.  full: those that
  * wrote every plane (every form and operator); reused: PNP assemblies that kept the
- * stored constant planes (PNP_OPT_ASM_REUSE_CONST).  Either pointer may be NULL. */
-int pnp_asm_info(pnp_ctx *ctx, int64_t *full, int64_t *reused);
+ * stored constant planes (PNP_OPT_ASM_REUSE_CONST); pipelined: those among the reused ones that
+ * ran as the persistent, prefetching walk (the environment variable PNP_ASM_PIPE=0/1, read once per
+ * process, chooses it for the warm constant-planes assembly; PNP_ASM_PIPE_GRID=n caps its grid at
+ * n workgroups).  Any pointer may be NULL. */
+int pnp_asm_info(pnp_ctx *ctx, int64_t *full, int64_t *reused, int64_t *pipelined);
+/* The flag byte per vertex that the P1 assembly's residual tail reads for the operator set now,
+ * flags[nv_global] in global vertex order (0xff: not a row of this rank).  Bits 0 .. nfields-1: the
+ * row's Dirichlet mask; bit 3 (PNP_ROW_FLAG_LOAD): some entry of the row's constant load (Neumann
+ * flux + c_extra) or of c_extra itself is not bitwise +0.0 (-0.0 counts), or the operator is an
+ * implicit Euler one (the old time level's mass is in every row's load) -- only those rows read the
+ * load, the others add +0.0.  P1 contexts only. */
+#define PNP_ROW_FLAG_LOAD 8
+int pnp_asm_row_flags(pnp_ctx *ctx, uint8_t *flags);
 /* PNP_OPT_MATRIX_FREE's counters, since the context was created.  applies: matrix-free operator
  * applications launched (the interior + boundary pair of a halo-overlapped application counts
  * once, as does an application captured into a replayed graph).  value_assemblies: assemblies

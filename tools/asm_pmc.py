@@ -6,7 +6,13 @@ cache scrubs (k_scrub, 64 MiB):
   warm     10 assemblies back to back (after 2 untimed ones), bench.py's `value` regime;
   in_situ  10 x (20 BiCGSTAB + ILU(0) iterations, then one assembly), as Newton runs it;
   cold     10 x (1 GiB scrub, then one assembly).
-Run it under rocprofv3 once per counter set (`--pmc <set> --kernel-trace`, the program after --).
+Run it under rocprofv3 once per counter set (`--pmc <set>`, the program after --; a counter pass
+is a run of its own, never combined with API or memory tracing).  The sets used so far: FETCH_SIZE;
+WRITE_SIZE; the L2-side sets of profiles/r06; and for the waves' stall picture (profiles/asm_pipe)
+`SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU
+GRBM_GUI_ACTIVE` and `SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR`: VALU-busy share of wave cycles =
+SQ_ACTIVE_INST_VALU / SQ_WAVE_CYCLES, wait share = SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES (both
+printed by split when the counters are there).
 
 Split (`python tools/asm_pmc.py split <out.json> <counter_collection.csv>...`): every dispatch of
 k_assemble_ga<0, ...> is attributed to its phase by its position in the fixed sequence; per phase
@@ -83,6 +89,10 @@ def split(out_path, paths):
             der["read_bytes_fetch_x2"] = 2 * d["FETCH_SIZE"] * 1024
         if "WRITE_SIZE" in d:
             der["write_bytes"] = d["WRITE_SIZE"] * 1024
+        if "SQ_WAVE_CYCLES" in d and "SQ_ACTIVE_INST_VALU" in d:
+            der["valu_busy_share_of_wave_cycles"] = d["SQ_ACTIVE_INST_VALU"] / d["SQ_WAVE_CYCLES"]
+        if "SQ_WAVE_CYCLES" in d and "SQ_WAIT_INST_ANY" in d:
+            der["wait_share_of_wave_cycles"] = d["SQ_WAIT_INST_ANY"] / d["SQ_WAVE_CYCLES"]
         if "TCC_HIT_sum" in d and "TCC_MISS_sum" in d:
             der["l2_hit_rate"] = d["TCC_HIT_sum"] / max(1.0, d["TCC_HIT_sum"] + d["TCC_MISS_sum"])
         out["phases"][p] = {"counters_mean_per_launch": d, "derived": der,
