@@ -23,6 +23,7 @@
 #include "../../include/pnp_capi.h"
 #include "amg.h"
 #include "gmres_small.h"
+#include "idr_small.h"
 #include "kernels.h"
 #include "mesh.h"
 #include "pk.h"
@@ -399,7 +400,14 @@ struct pnp_ctx {
   int gm_restart = 30;  // PNP_OPT_GMRES_RESTART
   DBuf<double> gm_V, gm_Z, gm_part, gm_hist;
   DBuf<pnp::GmresState> gm_S;
-  std::vector<double> gm_history;  // the last GMRES / FGMRES solve's (pnp_solve_history)
+  std::vector<double> gm_history;  // the last GMRES / FGMRES / IDR solve's (pnp_solve_history)
+  // IDR(s) (idr()): the n x s arrays G (owned rows), U (with ghosts) and the shadow matrix P, the
+  // reductions' partials, the device state block and history; allocated on first use
+  int idr_s = pnp::kIdrDefaultS;  // PNP_OPT_IDR_S
+  int idr_P_s = 0, idr_P_nf = 0;  // what idr_P was generated for (0: not generated)
+  DBuf<double> idr_G, idr_U, idr_P, idr_part, idr_hist;
+  DBuf<pnp::IdrState> idr_S;
+  long long idr_replacements = 0;  // residual replacements since the context was created
 
   // timers / debugging
   bool timing = false;
@@ -2648,6 +2656,236 @@ struct pnp_ctx {
     return PNP_OK;
   }
 
+  // IDR(s), bi-orthogonal variant, on J zout = bdev (owned rows), zero start, right-preconditioned:
+  // the monitored norm is the true system's residual's.  DESIGN.md 4.10.  The state (M, f, c,
+  // alpha, beta, omega, counters, flags) lives on the device (idr_small.h); the host enqueues the
+  // fixed sequence step 0 .. s - 1, omega step, step 0, ... and reads the state's header only at
+  // the check_every poll.  When the recurrence's norm meets the test (or at maxit, or on a
+  // breakdown) the device enters phase 2 and every later step kernel idles; the host, once a poll
+  // shows it, forms r = b - A x and the device judges the true norm: stop, or go on from that
+  // residual with G = U = 0, M = I, omega = 1 (a residual replacement).
+  long long idr_ld(bool ghosts) const {
+    const size_t rows = ghosts ? size_t(dl.n_local) : size_t(L.n_owned);
+    return (long long)((size_t(nf) * rows + 1) & ~size_t(1));
+  }
+  void idr_free() {
+    idr_G.release();
+    idr_U.release();
+    idr_P.release();
+    idr_part.release();
+    idr_P_s = idr_P_nf = 0;
+  }
+  // the shadow matrix for the current s and field count: counter-based entries by global vertex,
+  // then modified Gram-Schmidt with one reduction (and allreduce) per dot product
+  int idr_shadow_build() {
+    const int s = idr_s;
+    if (idr_P_s == s && idr_P_nf == nf && idr_P.p) return PNP_OK;
+    const long long n = nown(), ldg = idr_ld(false);
+    const int nps = pnp::idr_nparts(n);
+    hipError_t e = hipSuccess;
+    idr_P_s = idr_P_nf = 0;
+    if (idr_P.n != size_t(ldg) * s) e = idr_P.alloc(size_t(ldg) * s);
+    if (e == hipSuccess && idr_part.n != size_t(nps) * (pnp::kIdrMaxS + 4))
+      e = idr_part.alloc(size_t(nps) * (pnp::kIdrMaxS + 4));
+    if (e == hipSuccess && !idr_S.p) e = idr_S.alloc(1);
+    if (e == hipSuccess)
+      e = pnp::launch_idr_shadow_fill(L.n_owned, nf, s, d_l2g.p, idr_P.p, ldg, stream);
+    if (e != hipSuccess) return hipfail(e, "idr shadow");
+    auto col = [&](int j) { return idr_P.p + size_t(j) * size_t(ldg); };
+    int rc;
+    for (int j = 0; j < s; j++) {
+      for (int i = 0; i <= j; i++) {  // i == j: the norm
+        e = pnp::launch_idr_dot(idr_S.p, col(i), col(j), n, idr_part.p, nps, stream);
+        if (e != hipSuccess) return hipfail(e, "idr shadow");
+        if ((rc = allreduce_dev(pnp::idr_red(idr_S.p), 1))) return rc;
+        e = pnp::launch_idr_mgs(idr_S.p, col(j), i < j ? col(i) : nullptr, n, stream);
+        if (e != hipSuccess) return hipfail(e, "idr shadow");
+      }
+    }
+    idr_P_s = s;
+    idr_P_nf = nf;
+    return PNP_OK;
+  }
+  int idr_alloc() {
+    const int s = idr_s;
+    const size_t ldg = size_t(idr_ld(false)), ldu = size_t(idr_ld(true));
+    hipError_t e = hipSuccess;
+    if (idr_G.n != ldg * s) e = idr_G.alloc(ldg * s);
+    if (e == hipSuccess && idr_U.n != ldu * s) e = idr_U.alloc(ldu * s);
+    if (e != hipSuccess) return hipfail(e, "idr arrays");
+    return idr_shadow_build();
+  }
+
+  int idr(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res) {
+    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
+    if (o.maxit < 0) return fail(PNP_E_ARG, "maxit must not be negative");
+    static_assert(offsetof(pnp::IdrState, red) <= sizeof(pnp::Scalars), "poll staging");
+    const size_t hdr = offsetof(pnp::IdrState, red);
+    double t_start = now_s();
+    const long long n = nown();
+    const int s = idr_s, prec = o.prec;
+    int rc;
+    if ((rc = idr_alloc())) return rc;
+    const long long ldg = idr_ld(false), ldu = idr_ld(true);
+    const int nps = pnp::idr_nparts(n);
+    hipError_t e = hipSuccess;
+    const int hcap = std::min(o.maxit, pnp::kIdrHistCap);
+    if (idr_hist.n < size_t(hcap) + 2) e = idr_hist.alloc(size_t(hcap) + 2);
+    if (e != hipSuccess) return hipfail(e, "idr history");
+    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
+    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
+    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
+    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
+    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
+    pnp::IdrState *St = idr_S.p;
+    pnp::IdrState *hp = reinterpret_cast<pnp::IdrState *>(hS);  // header only
+    double *red = pnp::idr_red(St);
+    {
+      pnp::IdrState *init = reinterpret_cast<pnp::IdrState *>(hS + 2);
+      std::memset(init, 0, hdr);
+      init->reduction = o.reduction;
+      init->omega = 1.0;
+      init->s = s;
+      init->maxit = o.maxit;
+      init->phase = 2;  // the start is a judged residual like any other
+      init->hcap = hcap;
+      e = hipMemcpyAsync(St, init, hdr, hipMemcpyHostToDevice, stream);
+    }
+    if (e == hipSuccess) e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(rs.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return hipfail(e, "idr init");
+    auto G = [&](int i) { return idr_G.p + size_t(i) * size_t(ldg); };
+    auto U = [&](int i) { return idr_U.p + size_t(i) * size_t(ldu); };
+    auto allred = [&](int k) -> int {
+      if (!dist) return PNP_OK;
+      hipEvent_t t0 = tb(T_ALLRED);
+      int r2 = allreduce_dev(red, k);
+      if (r2) return r2;
+      te(T_ALLRED, t0);
+      return PNP_OK;
+    };
+    auto small = [&](int which, int hk) -> int {
+      hipError_t e2 = pnp::launch_idr_small(St, idr_hist.p, which, hk, stream);
+      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "idr state");
+    };
+    // rs holds a true residual: its norm and P^T rs, the verdict, and a clean start if it goes on
+    auto begin = [&](int first) -> int {
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_idr_resid_dots(St, s, rs.p, idr_P.p, ldg, n, idr_part.p, nps, stream);
+      if (e2 == hipSuccess) e2 = hipMemsetAsync(idr_G.p, 0, sizeof(double) * idr_G.n, stream);
+      if (e2 == hipSuccess) e2 = hipMemsetAsync(idr_U.p, 0, sizeof(double) * idr_U.n, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr residual");
+      te(T_BLAS, t0);
+      int r2 = allred(s + 1);
+      if (r2) return r2;
+      return small(4, first);
+    };
+    auto step = [&](int hk) -> int {
+      int nsp = 0, r2;
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_idr_v(St, hk, rs.p, idr_G.p, ldg, n, t.p, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr v");
+      te(T_BLAS, t0);
+      const double *vh = t.p;
+      if (prec != PNP_PREC_NONE) {
+        if ((r2 = precond(prec, t.p, y.p))) return r2;
+        vh = y.p;
+      }
+      t0 = tb(T_BLAS);
+      if ((e2 = pnp::launch_idr_u(St, hk, vh, idr_U.p, ldu, n, stream)) != hipSuccess)
+        return hipfail(e2, "idr u");
+      te(T_BLAS, t0);
+      if ((r2 = halo_spmv(U(hk), G(hk), 0, nullptr, nullptr, &nsp))) return r2;
+      t0 = tb(T_BLAS);
+      e2 = pnp::launch_idr_ptg(St, hk, s, idr_G.p, ldg, idr_P.p, n, idr_part.p, nps, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr shadow products");
+      te(T_BLAS, t0);
+      if ((r2 = allred(s))) return r2;
+      t0 = tb(T_BLAS);
+      if ((r2 = small(0, hk))) return r2;
+      e2 = pnp::launch_idr_update(St, hk, idr_G.p, ldg, idr_U.p, ldu, rs.p, zout, n, idr_part.p,
+                                  nps, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr update");
+      te(T_BLAS, t0);
+      if ((r2 = allred(1))) return r2;
+      return small(1, hk);
+    };
+    auto omega_step = [&]() -> int {
+      int nsp = 0, r2;
+      double *vh = rs.p;
+      if (prec != PNP_PREC_NONE) {
+        if ((r2 = precond(prec, rs.p, y.p))) return r2;
+        vh = y.p;
+      } else {  // the SpMV's input carries ghosts, which the exchange writes: not into rs
+        hipError_t e2 = hipMemcpyAsync(y.p, rs.p, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
+        if (e2 != hipSuccess) return hipfail(e2, "idr copy");
+        vh = y.p;
+      }
+      if ((r2 = halo_spmv(vh, t.p, 0, nullptr, nullptr, &nsp))) return r2;
+      hipEvent_t t0 = tb(T_BLAS);
+      hipError_t e2 = pnp::launch_idr_om_dots(St, t.p, rs.p, n, idr_part.p, nps, stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr omega");
+      te(T_BLAS, t0);
+      if ((r2 = allred(3))) return r2;
+      t0 = tb(T_BLAS);
+      if ((r2 = small(2, 0))) return r2;
+      e2 = pnp::launch_idr_om_update(St, s, t.p, vh, rs.p, zout, idr_P.p, ldg, n, idr_part.p, nps,
+                                     stream);
+      if (e2 != hipSuccess) return hipfail(e2, "idr omega update");
+      te(T_BLAS, t0);
+      if ((r2 = allred(s + 1))) return r2;
+      return small(3, 0);
+    };
+    auto poll = [&]() -> int {
+      hipError_t e2 = hipMemcpyAsync(hp, St, hdr, hipMemcpyDeviceToHost, stream);
+      if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
+      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "idr poll");
+    };
+    if ((rc = begin(1))) return rc;
+    const int check = o.check_every > 0 ? o.check_every : 8;
+    int hk = 0, it_known = 0;  // hk == s: the omega step is next
+    if ((rc = poll())) return rc;
+    while (!hp->done) {
+      // applications until the next poll: never past maxit, and one at a time once the norm is
+      // within a decade of the target (an application enqueued after the recurrence has ended
+      // costs a preconditioner application and an SpMV for nothing)
+      const bool near = hp->norm < 10.0 * o.reduction * hp->norm0;
+      const int ns = std::max(1, std::min(near ? 1 : check, o.maxit - it_known));
+      for (int q = 0; q < ns; q++) {
+        if ((rc = hk < s ? step(hk) : omega_step())) return rc;
+        hk = hk < s ? hk + 1 : 0;
+      }
+      if ((rc = poll())) return rc;
+      if (hp->done) break;
+      if (hp->phase == 2) {  // the recurrence has ended: the true residual decides
+        int nsp = 0;
+        if ((rc = halo_spmv(zout, rs.p, 3, bdev, nullptr, &nsp))) return rc;  // r = b - A x
+        if ((rc = begin(0))) return rc;
+        hk = 0;
+        if ((rc = poll())) return rc;
+      }
+      it_known = hp->it;
+    }
+    if (prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
+    if (prec == PNP_PREC_ILU0 && (rc = ilu_flow_check())) return rc;
+    gm_history.assign(size_t(std::min(hp->it, hcap)) + 1, 0.0);
+    e = hipMemcpyAsync(gm_history.data(), idr_hist.p, sizeof(double) * gm_history.size(),
+                       hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "idr history");
+    idr_replacements += hp->replacements;
+    res.converged = hp->done == 1 ? 1 : 0;
+    res.breakdown = hp->breakdown;
+    res.iterations = hp->it;
+    res.it_half = hp->it;
+    res.defect0 = hp->norm0;
+    res.defect = hp->norm;
+    res.reduction = hp->norm0 > 0 ? hp->norm / hp->norm0 : 0.0;
+    res.elapsed = now_s() - t_start;
+    return PNP_OK;
+  }
+
   // ---- reference-order mode (PNP_OPT_SEQ_ORDER) ------------------------------------------------
   // The reference's single-rank arithmetic in its order (seq_order.hip): element-order assembly
   // into the CSR view, ISTL's sequential mv / dot / updates, the scalar recurrences here in double.
@@ -3000,6 +3238,9 @@ struct pnp_ctx {
     } else if (o.method == PNP_METHOD_GMRES || o.method == PNP_METHOD_FGMRES) {
       amg_symmetric = false;
       rc = gmres(bdev, zout, o, res, o.method == PNP_METHOD_FGMRES);
+    } else if (o.method == PNP_METHOD_IDR) {
+      amg_symmetric = false;
+      rc = idr(bdev, zout, o, res);
     } else {
       return fail(PNP_E_ARG, "unknown solver method");
     }
@@ -4320,6 +4561,15 @@ extern "C" int pnp_set_option(pnp_ctx *c, int32_t option, int64_t value) {
     }
     return PNP_OK;
   }
+  if (option == PNP_OPT_IDR_S) {
+    if (!pnp::idr_s_valid(value)) return c->fail(PNP_E_ARG, "PNP_OPT_IDR_S takes 1 .. 8");
+    if (c->idr_s != int(value)) {
+      hipSetDevice(c->device);
+      c->idr_free();
+      c->idr_s = int(value);
+    }
+    return PNP_OK;
+  }
   if (option == PNP_OPT_BICG_TWORED) {
     if (value < -1 || value > 1) return c->fail(PNP_E_ARG, "PNP_OPT_BICG_TWORED takes -1, 0 or 1");
     c->twored_opt = int(value);
@@ -4450,6 +4700,10 @@ extern "C" int pnp_get_option(pnp_ctx *c, int32_t option, int64_t *value) {
     *value = c->asm_reuse_opt;
     return PNP_OK;
   }
+  if (option == PNP_OPT_IDR_S) {
+    *value = c->idr_s;
+    return PNP_OK;
+  }
   return c->fail(PNP_E_ARG, "unknown option");
 }
 
@@ -4458,6 +4712,21 @@ extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_ass
   if (applies) *applies = c->mf_applies;
   if (value_assemblies) *value_assemblies = c->value_assemblies;
   return PNP_OK;
+}
+
+extern "C" int pnp_idr_info(pnp_ctx *c, int64_t *replacements) {
+  if (!c) return PNP_E_ARG;
+  if (replacements) *replacements = c->idr_replacements;
+  return PNP_OK;
+}
+
+extern "C" int pnp_idr_shadow(pnp_ctx *c, int32_t j, double *p) {
+  if (!c || !p) return PNP_E_ARG;
+  if (!c->idr_P.p || c->idr_P_s != c->idr_s || c->idr_P_nf != c->nf)
+    return c->fail(PNP_E_STATE, "no IDR solve yet with the current PNP_OPT_IDR_S and operator");
+  if (j < 0 || j >= c->idr_s) return c->fail(PNP_E_ARG, "shadow column out of range");
+  hipSetDevice(c->device);
+  return c->download_ext(c->idr_P.p + size_t(j) * size_t(c->idr_ld(false)), c->nf, p);
 }
 
 extern "C" int pnp_asm_row_flags(pnp_ctx *c, uint8_t *flags) {

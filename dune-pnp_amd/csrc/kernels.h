@@ -621,6 +621,50 @@ hipError_t launch_gmres_norm2(GmresState *S, const double *a, long long n, doubl
 hipError_t launch_gmres_restart(GmresState *S, double *hist, int first, double *V, long long ld,
                                 long long n, const double *r, hipStream_t s);
 
+// ---- IDR(s) (idr.hip; the state block and the small dense part in idr_small.h) -----------------
+// G, P: s columns of owned rows, column i at + i * ldg; U: s columns that carry their ghosts, at
+// + i * ldu (both leading dimensions even, >= n = n_owned * nf).  part: kIdrMaxS + 4 rows of nps
+// partials; idr_nparts(n) <= nps workgroups write them.  hk: the host's step index; a launch does
+// nothing unless the state's phase and k are the ones it was enqueued for.  Every reduction ends
+// in S->red (idr_red(S): the device address the allreduce works on).
+struct IdrState;
+int idr_nparts(long long n);
+double *idr_red(IdrState *S);
+// v = r - sum_{i>=k} c_i G_i
+hipError_t launch_idr_v(const IdrState *S, int hk, const double *r, double *G, long long ldg,
+                        long long n, double *v, hipStream_t st);
+// U_k = omega vh + sum_{i>=k} c_i U_i
+hipError_t launch_idr_u(const IdrState *S, int hk, const double *vh, double *U, long long ldu,
+                        long long n, hipStream_t st);
+// red[0 .. s) = P^T G_k (this rank's part)
+hipError_t launch_idr_ptg(IdrState *S, int hk, int s, const double *G, long long ldg,
+                          const double *P, long long n, double *part, int nps, hipStream_t st);
+// one thread of idr_small.h: which 0 idr_step_a, 1 idr_step_b, 2 idr_omega, 3 idr_omega_end,
+// 4 idr_begin (hk = first)
+hipError_t launch_idr_small(IdrState *S, double *hist, int which, int hk, hipStream_t st);
+// G_k -= sum_{i<k} alpha_i G_i, U_k likewise, r -= beta G_k, x += beta U_k; red[0] = ||r||^2
+hipError_t launch_idr_update(IdrState *S, int hk, double *G, long long ldg, double *U,
+                             long long ldu, double *r, double *x, long long n, double *part,
+                             int nps, hipStream_t st);
+// red[0 .. 3) = <t, r>, <t, t>, <r, r>
+hipError_t launch_idr_om_dots(IdrState *S, const double *t, const double *r, long long n,
+                              double *part, int nps, hipStream_t st);
+// r -= omega t, x += omega vh; red[0] = ||r||^2, red[1 .. s] = P^T r
+hipError_t launch_idr_om_update(IdrState *S, int s, const double *t, const double *vh, double *r,
+                                double *x, const double *P, long long ldp, long long n,
+                                double *part, int nps, hipStream_t st);
+// the same sums of a freshly formed residual (start, residual replacement)
+hipError_t launch_idr_resid_dots(IdrState *S, int s, double *r, const double *P, long long ldp,
+                                 long long n, double *part, int nps, hipStream_t st);
+// shadow matrix: counter-based entries by global vertex; red[0] = <a, b>; a -= red[0] src, or
+// (src null) a /= sqrt(red[0])
+hipError_t launch_idr_shadow_fill(int n_owned, int nf, int s, const int *l2g, double *P,
+                                  long long ldp, hipStream_t st);
+hipError_t launch_idr_dot(IdrState *S, const double *a, const double *b, long long n, double *part,
+                          int nps, hipStream_t st);
+hipError_t launch_idr_mgs(const IdrState *S, double *a, const double *src, long long n,
+                          hipStream_t st);
+
 // read n doubles of buf (cache scrub before a cache-cold timing; sink is never written)
 hipError_t launch_scrub(const double *buf, long long n, double *sink, hipStream_t s);
 

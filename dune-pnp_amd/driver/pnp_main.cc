@@ -12,8 +12,9 @@
 //                 [--matrix-free]  (PNP_OPT_MATRIX_FREE on every context: P1 only)
 //                 [--asm-full]  (PNP_OPT_ASM_REUSE_CONST = 0: every PnpOperator Jacobian assembly writes the
 //                                 state-independent planes too)
-//                 [--method bicgstab|cg|gmres|fgmres] [--restart m]  (the PNP phases' Krylov method,
-//                                 default bicgstab; m: the GMRES restart length, 2 .. 128, default 30)
+//                 [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]  (the PNP phases'
+//                                 Krylov method, default bicgstab; m: the GMRES restart length, 2 .. 128,
+//                                 default 30; s: IDR(s)'s shadow space dimension, 1 .. 8, default 4)
 //                 [--md-reduction r]
 //                 [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]
 //                 (bcgs_ssork, the reference's default: ISTL SeqSSOR in the lexicographic order,
@@ -60,7 +61,7 @@ static void usage() {
       "usage: pnp_main <config.cfg> [--refine k] [--mesh-scale s] [--mode stationary|instationary|md|pb]\n"
       "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec p]\n"
       "                [--device d] [--matrix-free] [--asm-full]\n"
-      "                [--method bicgstab|cg|gmres|fgmres] [--restart m]\n"
+      "                [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]\n"
       "                [--amg-smoother ssor|ilu0|jacobi]\n"
       "                [--out prefix] [--md-reduction r]\n"
       "                [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]\n"
@@ -203,6 +204,7 @@ int main(int argc, char **argv) {
   std::string linsolver = "bcgs_ssork";
   std::string method = "bicgstab";  // the Krylov method of the PNP phases (stationary / instationary)
   int restart = 0;                  // > 0: PNP_OPT_GMRES_RESTART
+  int idr_s = 0;                    // > 0: PNP_OPT_IDR_S
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -224,6 +226,7 @@ int main(int argc, char **argv) {
     else if (a == "--degree") degree = std::atoi(next().c_str());
     else if (a == "--method") method = next();
     else if (a == "--restart") restart = std::atoi(next().c_str());
+    else if (a == "--idr-s") idr_s = std::atoi(next().c_str());
     else if (a == "--matrix-free") matrix_free = true;
     else if (a == "--asm-full") asm_full = true;
     else if (a == "--reference-solvers") {
@@ -322,9 +325,11 @@ int main(int argc, char **argv) {
     if (method == "cg") pnp_method = PNP_METHOD_CG;
     else if (method == "gmres") pnp_method = PNP_METHOD_GMRES;
     else if (method == "fgmres") pnp_method = PNP_METHOD_FGMRES;
+    else if (method == "idr") pnp_method = PNP_METHOD_IDR;
     else if (method != "bicgstab") throw pnp_gpu::Error(PNP_E_ARG, "unknown --method " + method);
     if (restart > 0)
       pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_GMRES_RESTART, restart), ctx.get());
+    if (idr_s > 0) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_IDR_S, idr_s), ctx.get());
     pnp_gpu::BiCGStabBackend<V> ls(ctx, s.cfg.linear_solver_iterations, prec_of(prec),
                                    rank == 0 ? s.cfg.verbosity : 0, pnp_method);
     if (prec == "amg") amg_for("ilu0");

@@ -32,11 +32,11 @@ OK, E_ARG, E_HIP, E_RCCL, E_BREAKDOWN, E_NOT_CONVERGED, E_IO, E_MESH, E_STATE = 
     0, -1, -2, -3, -4, -5, -6, -7, -8
 OP_PNP, OP_PNP_IMPLICIT_EULER, OP_PB, OP_DIFF, OP_DIFF_IMPLICIT_EULER, OP_POISSON = range(6)
 PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL = range(6)
-METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES = 0, 1, 2, 3
+METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES, METHOD_IDR = 0, 1, 2, 3, 4
 (OPT_ILU_F32, OPT_ILU_FUSED_FACTOR, OPT_JAC_FD, OPT_BICG_TWORED, OPT_AMG_FALLBACK,
  OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
- OPT_GMRES_RESTART, OPT_MATRIX_FREE, OPT_ASM_REUSE_CONST) = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11,
-                                                             12, 13)
+ OPT_GMRES_RESTART, OPT_MATRIX_FREE, OPT_ASM_REUSE_CONST, OPT_IDR_S) = (1, 2, 3, 4, 5, 6, 7, 8,
+                                                                        9, 10, 11, 12, 13, 14)
 # environment variables of the library, read once per process (include/pnp_capi.h, pnp_asm_info):
 # the persistent, prefetching PNP assembly walk on / off, and a cap on its grid (A/B, tests)
 ASM_PIPE_ENV, ASM_PIPE_GRID_ENV = "PNP_ASM_PIPE", "PNP_ASM_PIPE_GRID"
@@ -655,7 +655,8 @@ class Context:
     def linear_solve(self, rhs, prec=PREC_NONE, reduction=1e-8, maxit=20000, check_every=8,
                      method=0):
         """method 0: ISTL BiCGSTABSolver, 1: ISTL CGSolver (METHOD_CG), 2 / 3: restarted GMRES /
-        flexible GMRES (METHOD_GMRES, METHOD_FGMRES; restart length OPT_GMRES_RESTART)."""
+        flexible GMRES (METHOD_GMRES, METHOD_FGMRES; restart length OPT_GMRES_RESTART), 4: IDR(s)
+        (METHOD_IDR; shadow space dimension OPT_IDR_S)."""
         rhs = self._vec(rhs)
         z = np.zeros_like(rhs)
         o = _SolveOpts(prec, reduction, maxit, check_every, method)
@@ -666,14 +667,28 @@ class Context:
         return z, {k: getattr(r, k) for k, _ in _SolveResult._fields_}
 
     def solve_history(self):
-        """Residual norms of the last linear_solve when it was GMRES / FGMRES: [0] = |r0|, [k] the
-        norm after Arnoldi step k (iterations + 1 values); empty after BiCGSTAB / CG."""
+        """Residual norms of the last linear_solve when it was GMRES / FGMRES / IDR: [0] = |r0|,
+        [k] the norm after Arnoldi step (IDR: operator application) k (iterations + 1 values);
+        empty after BiCGSTAB / CG."""
         n = C.c_int32(0)
         self._ck(lib().pnp_solve_history(self.h, None, 0, C.byref(n)))
         d = np.zeros(n.value)
         if n.value:
             self._ck(lib().pnp_solve_history(self.h, _ptr(d), n.value, C.byref(n)))
         return d
+
+    def idr_shadow(self, j):
+        """Column j of METHOD_IDR's shadow matrix (external layout, owned rows); E_STATE before the
+        first IDR solve with the current OPT_IDR_S and operator."""
+        p = np.zeros(self.nf * self.nn)
+        self._ck(lib().pnp_idr_shadow(self.h, int(j), _ptr(p)))
+        return p
+
+    def idr_info(self):
+        """METHOD_IDR's counter since the context was created: residual replacements."""
+        r = C.c_int64()
+        self._ck(lib().pnp_idr_info(self.h, C.byref(r)))
+        return {"replacements": r.value}
 
     def prec_apply(self, d, prec):
         """v = M^{-1} d for one preconditioner application on the last assembled Jacobian."""

@@ -315,7 +315,20 @@ enum { PNP_METHOD_BICGSTAB = 0, PNP_METHOD_CG = 1,
        PNP_METHOD_GMRES = 2,
        /* Flexible GMRES(m): the preconditioned basis Z is stored and x = x0 + Z y, so M may
         * differ from application to application (PNP_OPT_ILU_F32 = 3).  m more vectors. */
-       PNP_METHOD_FGMRES = 3 };
+       PNP_METHOD_FGMRES = 3,
+       /* IDR(s), the bi-orthogonal variant of van Gijzen and Sonneveld (2011), right-
+        * preconditioned: short recurrences, no restart, s = PNP_OPT_IDR_S shadow vectors.  Zero
+        * start; the monitored norm is the true system's recurrence residual, so `reduction` keeps
+        * its meaning.  iterations = it_half = operator applications inside the recurrence (s + 1
+        * per cycle), capped by maxit.  When the recurrence's norm meets the test (or at maxit),
+        * r = b - A x is recomputed (not counted) and its norm is the reported defect; a true norm
+        * that fails the test restarts the recurrence from that residual (a residual replacement,
+        * pnp_idr_info counts them; after 8 in one solve it stops unconverged).  breakdown 6: a
+        * zero or non-finite pivot of M = P^T G, or a zero or non-finite omega.  Works where GMRES
+        * works (every preconditioner, pnp_newton, PNP_DEVICE_PTRS, P_k and multi-rank contexts,
+        * PNP_OPT_MATRIX_FREE); not in reference-order mode, and PNP_OPT_GRAPH does not apply.
+        * DESIGN.md 4.10. */
+       PNP_METHOD_IDR = 4 };
 typedef struct {
   int32_t prec;       /* SSOR = one multicolour symmetric Gauss-Seidel sweep (k=1, w=1) */
   double reduction;   /* stop when ||r|| < reduction * ||r0|| (checked every half step) */
@@ -324,12 +337,13 @@ typedef struct {
   int32_t method;     /* PNP_METHOD_BICGSTAB (ISTL BiCGSTABSolver, the default),
                          PNP_METHOD_CG (ISTL CGSolver: LINEARSOLVER CG_NOPREC / CG_Jacobi,
                          src/instationary_pnp_from_pb_md.hh:198-206), PNP_METHOD_GMRES or
-                         PNP_METHOD_FGMRES (restarted / flexible GMRES, see above) */
+                         PNP_METHOD_FGMRES (restarted / flexible GMRES, see above),
+                         PNP_METHOD_IDR (IDR(s), see above) */
 } pnp_solve_opts;
 typedef struct {
   int32_t converged, iterations, breakdown; /* iterations = ceil(half-step counter); breakdown:
       1 rho, 2 omega, 3 h (ISTL's 1e-80 tests), 4 diverged (PNP_PREC_AMG only), 5 GMRES: zero
-      or non-finite Hessenberg column */
+      or non-finite Hessenberg column, 6 IDR: zero or non-finite pivot M[k,k] or omega */
   double it_half, defect0, defect, reduction, elapsed;
 } pnp_solve_result;
 
@@ -488,7 +502,11 @@ enum {
    * (implicit Euler) writes all planes on every assembly.  0: every Jacobian assembly writes all
    * planes (the environment variable PNP_ASM_REUSE_CONST=0/1 sets the default).  pnp_asm_info
    * counts both. */
-  PNP_OPT_ASM_REUSE_CONST = 13
+  PNP_OPT_ASM_REUSE_CONST = 13,
+  /* Dimension s of PNP_METHOD_IDR's shadow space: 1 .. 8, default 4 (other values: PNP_E_ARG).
+   * The n x s arrays (G, U and the shadow matrix P) are allocated at the first IDR solve;
+   * changing s frees them. */
+  PNP_OPT_IDR_S = 14
 };
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
 /* Jacobian assemblies that wrote the SELL values, since the context was created.  full: those that
@@ -512,6 +530,17 @@ int pnp_asm_row_flags(pnp_ctx *ctx, uint8_t *flags);
  * that wrote the SELL values, in either mode (with the option off: every Jacobian assembly).
  * Either pointer may be NULL. */
 int pnp_matfree_info(pnp_ctx *ctx, int64_t *applies, int64_t *value_assemblies);
+/* PNP_METHOD_IDR's counter, since the context was created.  replacements: residual replacements
+ * (the recurrence's norm met the test, the recomputed true norm did not, and the solve went on
+ * from the true residual).  The pointer may be NULL. */
+int pnp_idr_info(pnp_ctx *ctx, int64_t *replacements);
+/* Test hook: column j (0 <= j < PNP_OPT_IDR_S) of PNP_METHOD_IDR's shadow matrix P; p host,
+ * external [phi | c+ | c-] layout, owned rows (as pnp_prec_apply's vectors).  The entries come
+ * from a counter-based 64-bit mix of (global vertex, field, column, fixed seed) mapped to
+ * (-1, 1), so they do not depend on row order, colouring or partition; the columns are then
+ * orthonormalised once by modified Gram-Schmidt.  PNP_E_STATE before the first IDR solve with the
+ * current s and operator. */
+int pnp_idr_shadow(pnp_ctx *ctx, int32_t j, double *p);
 
 /* ---- creation options (process-wide; read by every later pnp_create / pnp_create_pk /
  * pnp_layout_build, since the row colouring and the layout are built at creation) ------------ */
@@ -538,7 +567,8 @@ int pnp_linear_solve_ex(pnp_ctx *ctx, const double *rhs, double *z, const pnp_so
 /* Residual history of the last pnp_linear_solve / pnp_linear_solve_ex on the context when it was
  * a GMRES or FGMRES solve: defects[0] = ||r0||, defects[k] = the residual norm after Arnoldi step
  * k -- the Givens estimate |g_{k+1}|; at each restart boundary and at the end the recomputed true
- * norm.  *n = iterations + 1 (at most cap values are written; defects may be null with cap 0).
+ * norm.  After an IDR solve: defects[k] = the recurrence's ||r|| after operator application k; at
+ * a residual replacement and at the end the recomputed true norm.  *n = iterations + 1 (at most cap values are written; defects may be null with cap 0).
  * After a BiCGSTAB or CG solve *n = 0.  Only the first 2^20 steps of a solve are kept (then
  * *n = 2^20 + 1 and the last kept entry is not the final norm; pnp_solve_result.defect is). */
 int pnp_solve_history(pnp_ctx *ctx, double *defects, int32_t cap, int32_t *n);
