@@ -340,8 +340,11 @@ struct pnp_ctx {
   bool vals_const_valid = false;
   // pnp_asm_info; asm_piped: launches of the persistent, prefetching walk (PNP_ASM_PIPE)
   long long asm_full = 0, asm_reused = 0, asm_piped = 0;
+  // (the variant exists for the gather-all walk only: layouts with a fan of more than 8 neighbours
+  // take launch_assemble's longer-fan walks, which write every plane and count as full writes)
   bool asm_kconst() const {
-    return asm_reuse_opt && vals_const_valid && degree == 1 && !fd_mode && kind == PNP_OP_PNP;
+    return asm_reuse_opt && vals_const_valid && degree == 1 && !fd_mode && kind == PNP_OP_PNP &&
+           dl.max_slots <= 9;
   }
   // bookkeeping after a launch that wrote vals: kc = it relied on the stored constant planes,
   // full = it was the P1 analytic assembly writing every plane

@@ -511,7 +511,8 @@ enum {
 int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
 /* Jacobian assemblies that wrote the SELL values, since the context was created.  full: those that
  * wrote every plane (every form and operator); reused: PNP assemblies that kept the
- * stored constant planes (PNP_OPT_ASM_REUSE_CONST); pipelined: those among the reused ones that
+ * stored constant planes (PNP_OPT_ASM_REUSE_CONST; meshes whose fans have at most 8 neighbours --
+ * a longer fan selects a walk that writes every plane, counted as full); pipelined: those among the reused ones that
  * ran as the persistent, prefetching walk (the environment variable PNP_ASM_PIPE=0/1, read once per
  * process, chooses it for the warm constant-planes assembly; PNP_ASM_PIPE_GRID=n caps its grid at
  * n workgroups).  Any pointer may be NULL. */

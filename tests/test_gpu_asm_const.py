@@ -16,8 +16,9 @@ writing every plane: its cases here check the equality with option 0 and that no
 assert_same_jacobian keeps the fallback the comparison was specified with (k0 / k1 entries bitwise,
 the rest within 1e-12 of max |J|); nothing takes it today.
 
-The goldens are small (a few hundred to a few thousand rows) with open and closed fans, fan
-breaks, Dirichlet rows, a last chunk and a last 256-row block that are not full.  The walk behind
+The goldens are small (a few hundred to a few thousand rows) with open and closed fans, Dirichlet
+rows, a last chunk and a last 256-row block that are not full; none of their rows has a fan break
+(the reuse walk on pinch vertices: tests/test_gpu_fan_walks.py).  The walk behind
 the variant (direct gathers or LDS-staged) is chosen once per process, so the reuse and cold-hint
 case also runs in child processes with PNP_ASM_LDS = 1 and 0, as test_gpu_asm_lds.py does."""
 import functools

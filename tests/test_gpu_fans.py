@@ -2,7 +2,9 @@
 at most 8 neighbours, which selects the gather-all walk (k_assemble_ga, FANR 9).  A wheel mesh
 with one high-degree hub exercises the other two paths: 11 neighbours (register-resident
 column indices, FANR 12) and 14 neighbours (index loads in the walk, FANR 0), for the fused
-residual + Jacobian and the residual-only (line search) kernels, against the oracle."""
+residual + Jacobian and the residual-only (line search) kernels, against the oracle; 30
+neighbours is the longest fan the layout accepts.  Open fans, pinch vertices and the other
+operators on these walks: tests/test_gpu_fan_walks.py."""
 import numpy as np
 import pytest
 
@@ -36,7 +38,7 @@ SURF = [dict(cb=1, cflux=0.3, cpot=0.0, pb=1, pflux=-0.2, pconc=0.0, mb=1, mflux
              mconc=0.07)]
 
 
-@pytest.mark.parametrize("k", [11, 14])
+@pytest.mark.parametrize("k", [11, 14, 30])  # 30: the longest fan the layout accepts, closed
 @pytest.mark.parametrize("kind", ["pnp", "pb"])
 def test_high_degree_fans_match_oracle(k, kind):
     xy, tri, bseg, bgroup = wheel(k)
