@@ -4058,6 +4058,9 @@ extern "C" int pnp_get_info(pnp_ctx *c, pnp_info *info) {
   info->uslots_live = c->uslots_live;
   info->lsx_entries = (int64_t)c->h_lsx_list.size();
   info->usx_entries = (int64_t)c->h_usx_list.size();
+  info->pk_split_short = c->pkd.n_short;
+  info->pk_split_long = c->pkd.n_long;
+  info->pk_split_len = c->pkd.short_len;
   size_t b = 0;
   b += c->vals.n * 8 + (c->x.n + c->r.n + c->rs.n + c->z.n + c->rt.n + c->p.n + c->v.n + c->t.n + c->y.n +
                         c->y2.n + c->b.n + c->prevu.n + c->ext.n) * 8 + c->ilu_y32buf.n * 4;

@@ -179,7 +179,8 @@ class _Info(C.Structure):
                 ("nat_flow_applies", C.c_int64), ("nat_level_applies", C.c_int64),
                 ("ilu_flow_applies", C.c_int64), ("lslots_live", C.c_int64),
                 ("uslots_live", C.c_int64), ("lsx_entries", C.c_int64),
-                ("usx_entries", C.c_int64)]
+                ("usx_entries", C.c_int64), ("pk_split_short", C.c_int32),
+                ("pk_split_long", C.c_int32), ("pk_split_len", C.c_int32)]
 
 
 class _SpaceInfo(C.Structure):

@@ -199,6 +199,11 @@ typedef struct {
                                        the lane padding; U with the diagonal slot) */
   int64_t lsx_entries, usx_entries; /* the LDS sweeps' staged neighbour rows, summed over the
                                        256-row blocks: the gathers of one ILU(0) application */
+  int32_t pk_split_short;  /* P_k Jacobian gather run as two launches: 256-row blocks in the launch
+                              with the short LDS accumulator; 0: one launch (or a P1 context) */
+  int32_t pk_split_long;   /* ... blocks in the launch with the max_slots accumulator; 0: one launch */
+  int32_t pk_split_len;    /* ... slots of the short accumulator (the median block's longest row);
+                              0: one launch */
 } pnp_info;
 int pnp_get_info(pnp_ctx *ctx, pnp_info *info);
 

@@ -2,7 +2,8 @@
 pinch vertices (several open fans around one vertex, so the row's fan carries break bits), open and
 closed fans up to the supported maximum of 30 neighbours, and systems of a handful of rows.  Plain
 numpy; tests/test_fan_layout_host.py walks them on the host, tests/test_gpu_fan_walks.py assembles
-them on the GPU.
+them on the GPU.  PK_TABLE lists the meshes of the P_k (degree 2, 3) assembly tests
+(tests/test_pk_edge_meshes_host.py on the host, tests/test_gpu_pk_edges.py on the GPU).
 
 Every generator returns (xy, tri, bseg, bgroup): CCW triangles, every boundary edge once in bseg as
 (low vertex, high vertex) in sorted order, and bgroup by one of two policies -- groups="zero" (one
@@ -100,6 +101,36 @@ def diamond_chain(n, groups="zero"):
     return _finish(xy, tri, groups)
 
 
+def wheel(k, groups="zero"):
+    """an interior hub 0 with one closed fan of k elements and k rim vertices, nothing else (the
+    wheel of tests/test_gpu_fans.py has two more rings around it, which P_k rows cannot afford: at
+    degree 2 this hub's row already couples to all 3k other nodes)"""
+    assert k >= 3
+    ang = 0.1 + 2 * np.pi * np.arange(k) / k
+    r = _radius(1 + np.arange(k))
+    xy = np.vstack([[0.0, Y0], np.c_[r * np.cos(ang), Y0 + r * np.sin(ang)]])
+    return _finish(xy, [(0, 1 + j, 1 + (j + 1) % k) for j in range(k)], groups)
+
+
+def wheel_on_chain(k, n, groups="zero"):
+    """diamond_chain(n) with a closed wheel of k rim vertices hung on its last joint 3n: hub 3n + 1
+    at (2n + 1.2, Y0), rim vertex 0 the joint itself (at angle pi from the hub), rim vertex j at
+    angle pi + 2 pi j / k and _radius(j) as vertex 3n + 1 + j.  The joint is a pinch vertex shared
+    by a chain quadrilateral and the wheel; the hub is interior, and its row is the only long one
+    among the many short rows of the chain."""
+    assert k >= 3
+    xy, tri, _, _ = diamond_chain(n)
+    hub, joint = 3 * n + 1, 3 * n
+    cx = 2.0 * n + 1.2
+    j = np.arange(1, k)
+    ang = np.pi + 2 * np.pi * j / k
+    rim = np.c_[cx + _radius(j) * np.cos(ang), Y0 + _radius(j) * np.sin(ang)]
+    xy = np.vstack([xy, [[cx, Y0]], rim])
+    ring = [joint] + [hub + int(q) for q in j]
+    tri = [tuple(t) for t in tri] + [(hub, ring[q], ring[(q + 1) % k]) for q in range(k)]
+    return _finish(xy, tri, groups)
+
+
 # (id, generator, argument tuple, rows, max_slots of the layout, rows with break bits, most break
 # bits in one row).  max_slots selects the walk: <= 9 the gather-all walk with 9 column registers
 # (FANR 9), <= 12 the pipelined walk with 12 (FANR 12), beyond it index loads in the walk (FANR 0).
@@ -136,6 +167,59 @@ def entry(mesh_id):
 
 def make(mesh_id, groups="zero"):
     _, gen, args, *_ = entry(mesh_id)
+    return gen(*args, groups=groups)
+
+
+# The P_k table: (id, generator, argument tuple, {degree: (nodes, longest row)}, elements, most
+# elements at one node, hub).  The longest row counts the diagonal, as pnp_info.max_slots does; a
+# row holds at most 63 slots.  hub: the node of the longest row is interior, so no boundary variant
+# constrains it and its row is compared in full (the boundary hubs of half_wheel and pinwheel sit
+# on segments of both groups and are Dirichlet nodes of the "alt" variant).  All figures from the
+# CPU oracle's P_k space; tests/test_pk_edge_meshes_host.py holds them to it.
+PK_TABLE = [
+    # one element: every node in exactly one element; 6 / 10 rows
+    ("one_triangle", one_triangle, (), {2: (6, 6), 3: (10, 10)}, 1, 1, False),
+    ("split_triangle", split_triangle, (), {2: (10, 10), 3: (19, 19)}, 3, 3, True),
+    # a hub in 4 and in 5 elements: one full batch of four incidence codes of the residual gather,
+    # and a batch with one live code
+    ("half_wheel_5", half_wheel, (5,), {2: (15, 15), 3: (28, 28)}, 4, 4, False),
+    ("half_wheel_6", half_wheel, (6,), {2: (18, 18), 3: (34, 34)}, 5, 5, False),
+    # 8 and 9 elements; (10) is the longest open fan a P3 row accepts
+    ("half_wheel_9", half_wheel, (9,), {2: (27, 27), 3: (52, 52)}, 8, 8, False),
+    ("half_wheel_10", half_wheel, (10,), {2: (30, 30), 3: (58, 58)}, 9, 9, False),
+    # 63 slots: the longest row the layout carries
+    ("half_wheel_21", half_wheel, (21,), {2: (63, 63)}, 20, 20, False),
+    ("wheel_10", wheel, (10,), {2: (31, 31), 3: (61, 61)}, 10, 10, True),  # P3's longest closed fan
+    ("wheel_20", wheel, (20,), {2: (61, 61)}, 20, 20, True),              # P2's; hub in 20 elements
+    ("pinwheel_3_1_2", pinwheel, ((3, 1, 2),), {2: (25, 25), 3: (46, 46)}, 6, 6, False),
+    ("pinwheel_1_1_1_1_1_2", pinwheel, ((1, 1, 1, 1, 1, 2),), {2: (34, 34), 3: (61, 61)}, 7, 7,
+     False),
+    ("diamond_chain_8", diamond_chain, (8,), {2: (65, 14)}, 16, 3, False),    # a SELL chunk + 1 row
+    ("diamond_chain_32", diamond_chain, (32,), {2: (257, 14)}, 64, 3, False),  # a workgroup + 1 row
+    ("diamond_chain_17", diamond_chain, (17,), {3: (256, 25)}, 34, 3, False),  # one workgroup
+    # 128 elements: one full workgroup of the Jacobian's element pass; 130: a last one of 2
+    ("diamond_chain_64", diamond_chain, (64,), {2: (513, 14), 3: (961, 25)}, 128, 3, False),
+    ("diamond_chain_65", diamond_chain, (65,), {2: (521, 14), 3: (976, 25)}, 130, 3, False),
+    # one 61-slot row among short chain rows, 4 / 7 blocks of 256 rows: the gather split runs
+    ("wheel_on_chain_20_100", wheel_on_chain, (20, 100), {2: (861, 61)}, 220, 20, True),
+    ("wheel_on_chain_10_100", wheel_on_chain, (10, 100), {3: (1561, 61)}, 210, 10, True),
+    # 2 blocks: the median block is the long one, no split
+    ("wheel_on_chain_20_31", wheel_on_chain, (20, 31), {2: (309, 61)}, 82, 20, True),
+    ("wheel_on_chain_10_16", wheel_on_chain, (10, 16), {3: (301, 61)}, 42, 10, True),
+]
+PK_IDS = [t[0] for t in PK_TABLE]
+PK_CASES = [(t[0], k) for t in PK_TABLE for k in sorted(t[3])]
+# (generator, argument tuple, degree, slots of its longest row): one node couples to more than 62
+PK_REFUSED = [(wheel, (21,), 2, 64), (half_wheel, (22,), 2, 66), (half_wheel, (11,), 3, 64),
+              (wheel, (11,), 3, 67)]
+
+
+def pk_entry(mesh_id):
+    return PK_TABLE[PK_IDS.index(mesh_id)]
+
+
+def pk_make(mesh_id, groups="zero"):
+    _, gen, args, *_ = pk_entry(mesh_id)
     return gen(*args, groups=groups)
 
 
