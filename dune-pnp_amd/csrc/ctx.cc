@@ -1,3256 +1,1760 @@
 // C-ABI implementation (include/pnp_capi.h): context, device buffers, halo exchange over RCCL,
 // device-resident BiCGSTAB (ISTL semantics) and PDELab-semantics Newton, host-orchestrated.
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <rocsolver/rocsolver.h>
+#include "ctx.h"
 
-#include <algorithm>
-#include <queue>
-#include <random>
-#include <chrono>
-#include <condition_variable>
-#include <map>
-#include <unordered_map>
-#include <mutex>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
+static thread_local std::string g_err;  // errors without a context (create / mesh calls)
+std::mutex g_groups_m;
+std::map<std::string, std::shared_ptr<LocalGroup>> g_groups;
 
-#include "../../include/pnp_capi.h"
-#include "amg.h"
-#include "gmres_small.h"
-#include "idr_small.h"
-#include "kernels.h"
-#include "mesh.h"
-#include "pk.h"
-
-namespace {
-
-thread_local std::string g_err;  // errors without a context (create / mesh calls)
-
-template <typename T>
-struct DBuf {
-  T *p = nullptr;
-  size_t n = 0;
-  hipError_t alloc(size_t count) {
-    release();
-    n = count;
-    if (count == 0) return hipSuccess;
-    hipError_t e = hipMalloc(&p, sizeof(T) * count);
-    if (e == hipSuccess) e = hipMemset(p, 0, sizeof(T) * count);  // no reliance on fresh pages
-    // the memset runs on the null stream, which does not order against the context's
-    // non-blocking streams: finish it before a kernel there writes the buffer (seen as zeroed
-    // FD element matrices with 8 in-process ranks competing for the GPU)
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
-    return e;
+// bookkeeping after a launch that wrote vals: kc = it relied on the stored constant planes,
+// full = it was the P1 analytic assembly writing every plane
+void pnp_ctx::asm_wrote(bool kc, bool full) {
+  if (kc) {
+    asm_reused++;
+  } else {
+    asm_full++;
+    vals_const_valid = full;
   }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    n = 0;
-  }
-  ~DBuf() { release(); }
-};
-
-enum TimerCat { T_ASM = 0, T_SPMV, T_PREC, T_BLAS, T_HALO, T_ALLRED, T_FACT, T_NCAT };
-
-double now_s() {
-  using namespace std::chrono;
-  return duration<double>(steady_clock::now().time_since_epoch()).count();
 }
 
-}  // namespace
-
-struct pnp_mesh_buf {
-  pnp::Mesh m;
-};
-
-// In-process communicator for tests on one GPU (pnp_comm::local_group): ranks are contexts in
-// one process, each driven by its own host thread.  Collectives are host barriers plus
-// device-to-device copies; every call synchronises, which is fine for correctness tests.
-struct LocalGroup {
-  int size = 0;
-  std::mutex m;
-  std::condition_variable cv;
-  int arrived = 0;
-  long generation = 0;
-  std::vector<pnp_ctx *> members;
-  std::vector<std::vector<double>> host;  // per-rank published host values (allreduce)
-  void barrier() {
-    std::unique_lock<std::mutex> lk(m);
-    long gen = generation;
-    if (++arrived == size) {
-      arrived = 0;
-      generation++;
-      cv.notify_all();
-    } else {
-      cv.wait(lk, [&] { return generation != gen; });
+pnp_ctx::~pnp_ctx() {
+  graphs_clear();
+  for (auto &v : ev_pending)
+    for (auto &pr : v) {
+      hipEventDestroy(pr.first);
+      hipEventDestroy(pr.second);
     }
-  }
-};
-static std::mutex g_groups_m;
-static std::map<std::string, std::shared_ptr<LocalGroup>> g_groups;
+  for (auto e : ev_pool) hipEventDestroy(e);
+  if (hS) hipHostFree(hS);
+  if (h_send) hipHostFree(h_send);
+  if (h_recv) hipHostFree(h_recv);
+  if (h_red) hipHostFree(h_red);
+  if (comm) ncclCommDestroy(comm);
+  if (blas) rocblas_destroy_handle(blas);
+  if (ev_ready) hipEventDestroy(ev_ready);
+  if (ev_halo) hipEventDestroy(ev_halo);
+  if (cstream) hipStreamDestroy(cstream);
+  if (stream) hipStreamDestroy(stream);
+}
 
-struct pnp_ctx {
-  std::string err;
-  int device = 0;
-  hipStream_t stream = nullptr;
-  int rank = 0, nranks = 1;
-  // the multi-rank code path (reduce -> allreduce -> derive, halo-split SpMV, two-reduction
-  // BiCGSTAB): more than one rank, or one rank with an RCCL communicator of its own (a pnp_comm of
-  // size 1 with an RCCL id -- the N > 1 path on one GPU, every allreduce a real ncclAllReduce)
-  bool dist = false;
-  ncclComm_t comm = nullptr;
-  std::shared_ptr<LocalGroup> lg;  // test transport instead of RCCL
-  pnp_host_transport ht{};         // host-staged transport (pnp_comm.host), if ht.exchange
-  double *h_send = nullptr, *h_recv = nullptr, *h_red = nullptr;  // its pinned staging buffers
-  size_t h_red_n = 0;
-  bool host_tr() const { return ht.exchange != nullptr; }
-
-  // P_k, k > 1 (pnp_create_pk): `mesh` is the node mesh (nv = Lagrange nodes, no elements) the
-  // partition, layout and external vectors are built on; tmesh the triangle mesh, pks the space
-  int degree = 1;
-  pnp::Mesh mesh, tmesh;
-  pnp::PkSpace pks;
-  pnp::PkDev pkd;
-  DBuf<int> pk_enode, pk_ioff, pk_icnt, pk_inc;
-  DBuf<uint32_t> pk_islot;
-  DBuf<double> pk_eres, pk_ejac;
-  DBuf<int> pk_blk_short, pk_blk_long;
-  pnp::Params params;
-  pnp::Fans fans;
-  pnp::LocalLayout L;
-  pnp::DevLayout dl;
-
-  DBuf<int> d_chunk_len, d_chunk_off, d_colidx, d_l2g, d_send_idx, d_color_idx;
-  DBuf<uint8_t> d_rowcolor;
-  DBuf<uint64_t> d_rowmeta;
-  DBuf<int> d_uptr, d_ulist;   // LDS-staged SpMV lists (PNP_SPMV_LDS, DevLayout::uptr)
-  DBuf<int> d_uown;            // per block: list entries before its own rows (DevLayout::uown)
-  DBuf<int> d_lsx_ptr, d_lsx_list, d_usx_ptr, d_usx_list;  // LDS-staged sweeps (DevLayout lsx_*)
-  DBuf<uint16_t> d_lsx_idx, d_usx_idx;
-  DBuf<uint8_t> d_lperm, d_uperm, d_lpinv, d_upinv, d_llen, d_ulen, d_ldl;  // split lane order
-  DBuf<uint16_t> d_lidx;
-  DBuf<double> d_xy;
-
-  // operator
-  int kind = -1, nf = 0, pat = 0, nvb = 0, nks = 0;  // nvb: block pattern size, nks: stored
-  std::vector<uint8_t> hmask;  // Dirichlet mask of the current operator, owned rows x nf
-  pnp::AsmArgs aa{};
-  DBuf<double> vals, lu;  // matrix and its ILU(0) factors
-  bool lu_valid = false;
-  // triangular split storage (DevLayout l*/u*): lvals/uvals hold either the matrix (SSOR) or the
-  // ILU(0) factors; split_of says which is current (0 none, 1 matrix, 2 factors)
-  DBuf<int> d_lchunk_len, d_lchunk_off, d_lcolidx, d_lsrc, d_uchunk_len, d_uchunk_off, d_ucolidx,
-      d_usrc;
-  DBuf<double> lvals, uvals, tsgs;
-  int split_of = 0;
-  // ILU(0) factors in the split storage in single precision (PNP_OPT_ILU_F32, default 1; the
-  // sweeps compute in fp64, the matrix, SpMV, SSOR and every vector stay fp64).  Measured at
-  // config 3: ILU(0) apply 119 -> 95 us, BiCGSTAB 428 -> 389 us/it, Newton 9,295 -> 9,177
-  // iterations (profiles/r02/ab_ilu_f32.log)
-  // 2 (the default since round 5): bfloat16 factors for block systems (linalg.hip bf16s: 14 B per
-  // PNP block instead of 28 -- 16 B until ILU_BF16_B7; ILU(0) apply 66.3 -> 58.6 us, BiCGSTAB 0.285 -> 0.270 ms per
-  // iteration at config 3, Newton counts inside their last-bit spread); scalar
-  // systems (PB, Poisson, diffusion: one value per block, 2 B saved per slot) keep f32, where the
-  // PB Newton at config 1 took 13 % more iterations with bf16
-  // 3 (opt-in): the bf16 factors of 2, and the forward sweep's intermediate y = L^-1 d kept in
-  // single precision (ilu_y32: 12 B per PNP row written, re-read by the backward sweep and gathered
-  // by the forward one, instead of 24): apply 56.3 -> 54.5 us at config 3, but the rounding makes
-  // the preconditioner nonlinear (2-5e-8 relative per application), which BiCGSTAB's short
-  // recurrences do not tolerate: 408 -> 710 iterations on a config-5 solve, the config-5 Newton
-  // and the config-4 AMG steps stall, so not the default.  The dataflow form (PNP_OPT_ILU_FLOW) keeps y in fp64 and runs
-  // 3 as 2
-  int ilu_f32 = [] {
-    const char *e = std::getenv("PNP_ILU_F32");
-    const int v = e ? std::atoi(e) : 2;
-    return (v >= 0 && v <= 3) ? v : 2;
+// rocprofv3 (ROCm 7.2) --kernel-trace dies with SIGSEGV once it has traced some 12,000-15,000
+// graph-launched kernels, whatever the graph (tools/micro/graph_capture_prof.hip):
+// under the profiler (its launcher exports ROCPROF_* variables) graph replay stays off unless
+// PNP_OPT_GRAPH forces it; the eager launches give the same results bit for bit
+bool pnp_ctx::profiled() {
+  static const bool p = [] {
+    extern char **environ;
+    for (char **e = environ; e && *e; e++)
+      if (std::strncmp(*e, "ROCPROF_", 8) == 0) return true;
+    return false;
   }();
-  int ilu_eff() const { return (ilu_f32 >= 2 && nf == 1) ? 1 : ilu_f32; }
-  // the factors' storage: 0 fp64, 1 f32, 2 bf16 (the kernels' f32 argument)
-  int ilu_fac() const { return ilu_eff() == 3 ? 2 : ilu_eff(); }
-  int f32_now() const { return split_of == 2 ? ilu_fac() : 0; }
-  // the single-precision forward intermediate of the colour launches, or null
-  DBuf<float> ilu_y32buf;
-  float *ilu_y32() const {
-    return (split_of == 2 && ilu_eff() == 3 && !ilu_flow_opt) ? ilu_y32buf.p : nullptr;
-  }
-  int ilu_fused = 1;  // PNP_OPT_ILU_FUSED_FACTOR
-  int amg_fallback = 0;  // PNP_OPT_AMG_FALLBACK
-  int ilu_retry = 1;     // PNP_OPT_ILU_RETRY
-  int twored_opt = [] {  // PNP_OPT_BICG_TWORED: -1 auto (on with more than one rank), 0, 1
-    const char *ev = std::getenv("PNP_BICG_TWORED");
-    return ev ? (std::atoi(ev) != 0 ? 1 : 0) : -1;
-  }();
-  DBuf<int> d_blkmap;
-  DBuf<int> d_rowoff, d_rowcol;  // row-contiguous block offsets / columns (fused ILU(0) factor)
-  // halo-overlapped SpMV (multi-GPU): 256-row blocks without / with ghost columns, each in the
-  // spatial order of blkmap; the halo runs on cstream while the interior blocks compute
-  DBuf<int> d_blk_int, d_blk_bnd;
-  int n_blk_int = 0, n_blk_bnd = 0;
-  bool split_spmv = false;
-  pnp::DevLayout sub_layout(bool interior) const {
-    pnp::DevLayout d = dl;
-    d.blkmap = interior ? d_blk_int.p : d_blk_bnd.p;
-    const int n = interior ? n_blk_int : n_blk_bnd;
-    d.blkcount = n > 0 ? n : -1;  // -1: no block (launch nothing)
-    return d;
-  }
-  hipStream_t cstream = nullptr;
-  hipEvent_t ev_ready = nullptr, ev_halo = nullptr;
-  DBuf<double> scrub;  // pnp_cache_scrub (cache-cold benchmark timings)
-  // forward-difference Jacobian (PNP_JAC_FD, fd_jacobian.hip): local elements, per-row block
-  // contribution lists, element matrices; built on first use
-  bool fd_built = false, fd_mode = false;
-  int fd_opt = 0;  // PNP_OPT_JAC_FD: every Jacobian assembly (Newton's too) by forward differences
-  int fd_ne = 0;
-  DBuf<int> fd_etri, fd_cdata;
-  DBuf<long long> fd_rptr;
-  DBuf<double> fd_jel;
-  // device CSR view (pnp_jacobian_csr_device): structure per block pattern, values per request
-  int csr_pat = -1, csr_nf = 0;
-  long long csr_nnz = 0;
-  DBuf<int> csr_rowptr, csr_col, csr_src;
-  DBuf<unsigned char> csr_vidx;
-  DBuf<double> csr_val;
-  bool csr_vals_valid = false;  // csr_val holds the current Jacobian
-  // natural-order SSOR (PNP_PREC_SSOR_NATURAL, ssor_natural.hip): level schedules of the forward
-  // and backward sweeps over the external-layout rows with each level's rows as an ELL over the
-  // CSR (pnp::NatSweep; built with the CSR structure), and external-layout work vectors
-  struct NatDir {
-    std::vector<int> lptr;
-    std::vector<long long> eoff;
-    DBuf<int4> info;
-    DBuf<int> ecol;
-    // the tail as chains (PNP_NAT_CHAIN): lane-group row lists, rows, padded entries
-    bool chain_ok = false;
-    int chain_groups = 0, chain_wpad = 0;
-    DBuf<int> cgptr, cecode;
-    DBuf<int4> crec;
-    pnp::NatFlow::Chains chains() const {
-      pnp::NatFlow::Chains c;
-      if (!chain_ok) return c;
-      c.ngroups = chain_groups;
-      c.wpad = chain_wpad;
-      c.gptr = cgptr.p;
-      c.rec = crec.p;
-      c.ecode = cecode.p;
-      return c;
-    }
-    pnp::NatSweep view() const {
-      pnp::NatSweep w;
-      w.nlev = int(lptr.size()) - 1;
-      w.lptr = lptr.data();
-      w.eoff = eoff.data();
-      w.info = info.p;
-      w.ecol = ecol.p;
-      return w;
-    }
-  };
-  NatDir nat_f, nat_b;
-  DBuf<double> nat_d, nat_v, nat_vf;  // external layout: d (level launches), vb, vf
-  DBuf<double> nat_di, nat_vi;        // internal layout temporaries (reference-order mode)
-  // the one-launch dataflow sweep (launch_ssor_natural_flow): units, forward units first
-  std::vector<int4> nat_units;
-  DBuf<int4> d_nat_units;
-  int nat_units_f = 0, nat_tail_f = 0, nat_tail_b = 0, nat_max_width = 0;
-  bool nat_units_ok = false;
-  DBuf<unsigned> nat_abort;  // [0]: set by a sweep whose operand wait timed out (sticky)
-  DBuf<int> csr_diag;        // index of each CSR-view row's diagonal entry
-  // ILU(0) application as one dataflow launch (PNP_OPT_ILU_FLOW, linalg.hip k_ilu0_flow): per
-  // c_first (0: every colour in the launch, 1: colour 0's forward step done by the update kernel)
-  // the unit table and dependency lists, built on first use from the staging lists (host copies
-  // kept from the layout build: rows at each L / U split position, lsx / usx lists)
-  int ilu_flow_opt = [] {
-    const char *e = std::getenv("PNP_ILU_FLOW");
-    return (e && std::atoi(e) != 0) ? 1 : 0;
-  }();
-  std::vector<int> h_posrowL, h_posrowU, h_lsx_ptr, h_lsx_list, h_usx_ptr, h_usx_list;
-  int64_t lslots_live = 0, uslots_live = 0;  // pnp_info
-  struct IluFlowDev {
-    bool built = false, ok = false;
-    pnp::IluFlow F;
-    DBuf<int> dep_ptr, dep_list;
-    DBuf<unsigned> flags;
-  };
-  IluFlowDev ilu_flow[2];
-  DBuf<unsigned> ilu_flow_abort;
-  bool ilu_flow_used = false;  // a flow launch ran since the last check
-  long long ilu_flow_n = 0;    // flow launches issued (pnp_info; a graph capture counts once)
-  // ---- reference-order mode (PNP_OPT_SEQ_ORDER, seq_order.hip) -----------------------------
-  int seq_opt = 0;
-  bool seq_built = false, seq_op_valid = false;
-  DBuf<int> seq_tri, seq_vptr, seq_vinc;
-  DBuf<double> seq_xy;
-  // the operator's data as the reference holds it: constrained rows (external layout), frozen
-  // fields, x_old, implicit-Euler dt / valency (host copies taken by pnp_set_operator)
-  std::vector<uint8_t> seq_mask_h;
-  std::vector<double> seq_phi_h, seq_cp_h, seq_cm_h, seq_xold_h;
-  double seq_dt = 0, seq_z = 0;
-  bool seq_cextra = false;
-  DBuf<unsigned char> seq_mask;
-  DBuf<int> seq_bptr;
-  DBuf<double> seq_bval, seq_phi, seq_cp, seq_cm, seq_xold;
-  DBuf<double> seq_rl, seq_rlt, seq_rlo, seq_jl, seq_jlt, seq_vec, seq_dotv;
-  int nat_pat = -1, nat_nf = 0;
-  // ion-current observable (pnp_ion_flux): boundary segments handled by this rank (the owner of
-  // the segment's lower global vertex), {a, c, opposite vertex, group} in local indices, in
-  // global segment order
-  DBuf<int4> d_fseg;
-  std::vector<int> fseg_group;
-  DBuf<double> fluxout, fluxx, fluxred;
-  DBuf<uint8_t> dmask;
-  // AsmArgs::rowflag of the operator set now: a byte per owned row, whole SELL chunks (padding 0)
-  DBuf<uint8_t> rowflag;
-  std::vector<uint8_t> hrowflag;  // its owned rows on the host (pnp_asm_row_flags)
-  DBuf<double> cvec, aux0, aux1;
-  bool assembled = false;
-  bool after_solve = false;  // a linear solve ran since the last Jacobian assembly (AsmArgs::cold)
-  // ---- matrix-free Jacobian application (PNP_OPT_MATRIX_FREE, jac_apply.hip) ----
-  // With the option on, a Jacobian "assembly" of a P1 analytic operator records the linearisation
-  // point (mf_x: the state with ghosts; mf_aa: the operator's arguments at that moment) and leaves
-  // the SELL values stale; halo_spmv and pnp_jacobian_apply compute J z from the point, and the
-  // consumers of vals (SSOR / ILU(0) / AMG set-up, the CSR view, the export) first run the
-  // ordinary assembly at the point (ensure_values).  mf_lin: the current Jacobian is held this
-  // way; vals_stale: vals does not hold it yet.
-  int mf_opt = 0;
-  bool mf_lin = false, vals_stale = false;
-  pnp::AsmArgs mf_aa{};
-  DBuf<double> mf_x, mf_r;  // the point; the residual ensure_values' fused assembly also writes
-  // Jacobi without SELL values: the diagonal blocks alone, one slot per chunk (launch_jac_diag),
-  // read by launch_jacobi through a layout whose chunk_off[c] = 64 c
-  DBuf<double> mf_diag;
-  DBuf<int> mf_choff;
-  bool mf_diag_valid = false;
-  long long mf_applies = 0, value_assemblies = 0;  // pnp_matfree_info
-  // ---- state-independent planes of the PNP k-form (PNP_OPT_ASM_REUSE_CONST) ----
-  // k0 / k1 of every PNP block depend on the mesh and the parameters only.
-  // vals_const_valid: vals holds them for the operator set now -- set by a P1 analytic assembly
-  // that wrote every plane, cleared by whatever else zeroes or writes vals (pnp_set_operator,
-  // set_fd, the FD and P_k Jacobians).  While it holds, the PNP Jacobian assembly leaves those
-  // planes alone (AsmArgs::kconst).
-  int asm_reuse_opt = [] {  // the environment variable PNP_ASM_REUSE_CONST=0/1 sets the default
-    const char *e = std::getenv("PNP_ASM_REUSE_CONST");
-    return (e && std::atoi(e) == 0) ? 0 : 1;
-  }();
-  bool vals_const_valid = false;
-  // pnp_asm_info; asm_piped: launches of the persistent, prefetching walk (PNP_ASM_PIPE)
-  long long asm_full = 0, asm_reused = 0, asm_piped = 0;
-  // (the variant exists for the gather-all walk only: layouts with a fan of more than 8 neighbours
-  // take launch_assemble's longer-fan walks, which write every plane and count as full writes)
-  bool asm_kconst() const {
-    return asm_reuse_opt && vals_const_valid && degree == 1 && !fd_mode && kind == PNP_OP_PNP &&
-           dl.max_slots <= 9;
-  }
-  // bookkeeping after a launch that wrote vals: kc = it relied on the stored constant planes,
-  // full = it was the P1 analytic assembly writing every plane
-  void asm_wrote(bool kc, bool full) {
-    if (kc) {
-      asm_reused++;
-    } else {
-      asm_full++;
-      vals_const_valid = full;
-    }
-  }
+  return p;
+}
 
-  // aggregation AMG (PNP_PREC_AMG, amg.h): the pattern hierarchy is built once per context (it
-  // depends on the layout only), the coarse values after every assembly
-  pnp_amg_opts amg_opts{PNP_PREC_SSOR, pnp::kAmgMaxCoarse, 12, 0.8, 2, -1};
-  bool amg_symmetric = true;  // set per solve: CG needs the symmetric V-cycle
-  std::vector<pnp::AmgLevelHost> amg_h;
-  struct AmgDev {
-    int nb = 0;
-    DBuf<int> rp, col, dpos, mptr, mem, agg, csrc;
-    DBuf<long long> cptr;
-    DBuf<double> v, dinv, b, x, x2;
-    DBuf<float> vf;  // single-precision values for the V-cycle's sweeps (amg_f32; null: fp64)
-  };
-  // PNP_AMG_F32 (default 1): the coarse levels' sweeps and residuals read single-precision block
-  // values, and the coarsest solve a single-precision copy of its inverse (the arithmetic, the
-  // Galerkin products, the diagonal inverses and the LU / inverse themselves stay fp64), as the
-  // ILU(0) factors do; 0 keeps fp64 (A/B)
-  static bool amg_f32() {
-    static const bool v = [] {
-      const char *e = std::getenv("PNP_AMG_F32");
-      return !(e && e[0] == '0');
-    }();
-    return v;
-  }
-  std::vector<std::unique_ptr<AmgDev>> amg_d;  // amg_d[k] = level k + 1
-  bool amg_built = false, amg_valid = false;
-  int amg_nf = 0;
-  double amg_setup_ms = 0;
-  DBuf<double> amg_ainv, amg_x0, amg_t, amg_y, amg_r, amg_z;
-  DBuf<float> amg_ainv_f;  // amg_f32(): the inverse in single precision, rows padded to amg_ld
-  int amg_ld = 0;
-  DBuf<int> amg_ipiv, amg_info;
-  rocblas_handle blas = nullptr;  // rocSOLVER getrf/getri of the AMG's coarsest level
+void pnp_ctx::graphs_clear() {
+  nat_graph_clear();
+  for (auto &g : graph_cache)
+    if (g.exec) hipGraphExecDestroy(g.exec);
+  graph_cache.clear();
+  graph_epoch++;
+  graphs_failed = false;
+}
 
-
-  // vectors (sized n_local * 3)
-  DBuf<double> x, r, rs, z, rt, p, v, t, y, y2, b, prevu, ext, sendbuf, partials, partials2;
-  DBuf<double> redmw;  // the multi-workgroup reduction's ticket and slice sums (main stream only)
-  std::vector<int> newton_its;        // pnp_newton_history: linear iterations per Newton step
-  std::vector<double> newton_defects; // and the defect after each step
-  DBuf<pnp::Scalars> S;
-  pnp::Scalars *hS = nullptr;  // pinned host mirror
-  // restarted GMRES / FGMRES (gmres()): basis V, preconditioned basis Z (flexible only), the
-  // orthogonalisation's partials, the device state block and history; allocated on first use
-  int gm_restart = 30;  // PNP_OPT_GMRES_RESTART
-  DBuf<double> gm_V, gm_Z, gm_part, gm_hist;
-  DBuf<pnp::GmresState> gm_S;
-  std::vector<double> gm_history;  // the last GMRES / FGMRES / IDR solve's (pnp_solve_history)
-  // IDR(s) (idr()): the n x s arrays G (owned rows), U (with ghosts) and the shadow matrix P, the
-  // reductions' partials, the device state block and history; allocated on first use
-  int idr_s = pnp::kIdrDefaultS;  // PNP_OPT_IDR_S
-  int idr_P_s = 0, idr_P_nf = 0;  // what idr_P was generated for (0: not generated)
-  DBuf<double> idr_G, idr_U, idr_P, idr_part, idr_hist;
-  DBuf<pnp::IdrState> idr_S;
-  long long idr_replacements = 0;  // residual replacements since the context was created
-
-  // timers / debugging
-  bool timing = false;
-  bool debug_trace = [] {
-    const char *e = std::getenv("PNP_DEBUG_BICGSTAB");
-    return e && std::atoi(e) != 0;
-  }();
-  std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_pending[T_NCAT];
-  std::vector<hipEvent_t> ev_pool;
-  double t_ms[T_NCAT] = {0};
-  long long t_n[T_NCAT] = {0};
-
-  ~pnp_ctx() {
-    graphs_clear();
-    for (auto &v : ev_pending)
-      for (auto &pr : v) {
-        hipEventDestroy(pr.first);
-        hipEventDestroy(pr.second);
-      }
-    for (auto e : ev_pool) hipEventDestroy(e);
-    if (hS) hipHostFree(hS);
-    if (h_send) hipHostFree(h_send);
-    if (h_recv) hipHostFree(h_recv);
-    if (h_red) hipHostFree(h_red);
-    if (comm) ncclCommDestroy(comm);
-    if (blas) rocblas_destroy_handle(blas);
-    if (ev_ready) hipEventDestroy(ev_ready);
-    if (ev_halo) hipEventDestroy(ev_halo);
-    if (cstream) hipStreamDestroy(cstream);
-    if (stream) hipStreamDestroy(stream);
-  }
-
-  // ---- hipGraph replay of BiCGSTAB iteration blocks (PNP_OPT_GRAPH) ------------------------------
-  // -1 auto: on for up to 131,072 owned rows (launch-bound sizes), 0 off, 1 on
-  int graph_opt = [] {
-    const char *e = std::getenv("PNP_GRAPH");
-    return e ? (std::atoi(e) != 0 ? 1 : 0) : -1;
-  }();
-  bool use_graphs() const {
-    return graph_opt == 1 || (graph_opt < 0 && L.n_owned <= (1 << 17) && !profiled());
-  }
-  // rocprofv3 (ROCm 7.2) --kernel-trace dies with SIGSEGV once it has traced some 12,000-15,000
-  // graph-launched kernels, whatever the graph (tools/micro/graph_capture_prof.hip):
-  // under the profiler (its launcher exports ROCPROF_* variables) graph replay stays off unless
-  // PNP_OPT_GRAPH forces it; the eager launches give the same results bit for bit
-  static bool profiled() {
-    static const bool p = [] {
-      extern char **environ;
-      for (char **e = environ; e && *e; e++)
-        if (std::strncmp(*e, "ROCPROF_", 8) == 0) return true;
-      return false;
-    }();
-    return p;
-  }
-  struct GraphKey {
-    int count, prec, fuse, nf, pat, f32, flow;
-    int mf;  // the operator application: 0 the SpMV, 1 matrix-free, 2 matrix-free with the SELL
-             // values stale (Jacobi then reads the diagonal blocks of jacobi_prepare())
-    const void *zout, *dmask;
-    long long epoch;
-    bool operator==(const GraphKey &o) const {
-      return count == o.count && prec == o.prec && fuse == o.fuse && nf == o.nf && pat == o.pat &&
-             f32 == o.f32 && flow == o.flow && mf == o.mf && zout == o.zout && dmask == o.dmask &&
-             epoch == o.epoch;
-    }
-  };
-  // kernel arguments captured in a graph stay valid while the buffers and the layout do: anything
-  // that changes an operator, an option or a buffer bumps the epoch
-  long long graph_epoch = 0;
-  bool graphs_failed = false;  // a capture / instantiation failed: eager launches from then on
-  struct GraphSlot {
-    GraphKey key;
-    hipGraphExec_t exec = nullptr;
-  };
-  std::vector<GraphSlot> graph_cache;
-  // the natural-order SSOR's level launches (ssor_natural.hip: ~2 x 131 levels per field sweep
-  // at pore_pnp k=3) replayed as one graph: their arguments are context buffers only
-  hipGraphExec_t nat_exec = nullptr;
-  bool nat_graph_failed = false;
-  void nat_graph_clear() {
-    if (nat_exec) hipGraphExecDestroy(nat_exec);
-    nat_exec = nullptr;
-    nat_graph_failed = false;
-  }
-  void graphs_clear() {
-    nat_graph_clear();
-    for (auto &g : graph_cache)
-      if (g.exec) hipGraphExecDestroy(g.exec);
-    graph_cache.clear();
-    graph_epoch++;
-    graphs_failed = false;
-  }
-  // replay the launches `issue` makes on the stream as a graph (captured on first use of `key`)
-  // *captured = false when the failure happened before any launch ran (capture / instantiate):
-  // the caller can then run the same iterations eagerly
-  template <typename F>
-  int graph_run(const GraphKey &key, F &&issue, bool *captured = nullptr) {
-    if (captured) *captured = true;
-    for (auto &g : graph_cache)
-      if (g.key == key) {
-        hipError_t e = hipGraphLaunch(g.exec, stream);
-        return e == hipSuccess ? PNP_OK : hipfail(e, "graph launch");
-      }
-    if (captured) *captured = false;
-    hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
-    if (e != hipSuccess) return hipfail(e, "graph capture");
-    const int rc = issue();
-    hipGraph_t graph = nullptr;
-    hipError_t e2 = hipStreamEndCapture(stream, &graph);
-    if (rc) {
-      if (graph) hipGraphDestroy(graph);
-      return rc;
-    }
-    if (e2 != hipSuccess) return hipfail(e2, "graph capture");
-    hipGraphExec_t exec = nullptr;
-    e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
-    hipGraphDestroy(graph);
-    if (e != hipSuccess) return hipfail(e, "graph instantiate");
-    if (captured) *captured = true;
-    if (graph_cache.size() >= 8) {
-      hipGraphExecDestroy(graph_cache.front().exec);
-      graph_cache.erase(graph_cache.begin());
-    }
-    graph_cache.push_back({key, exec});
-    e = hipGraphLaunch(exec, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "graph launch");
-  }
-
-  int fail(int code, const std::string &msg) {
-    err = msg;
-    return code;
-  }
-  int hipfail(hipError_t e, const char *what) {
-    err = std::string(what) + ": " + hipGetErrorString(e);
-    return PNP_E_HIP;
-  }
-
-  // ---- timers -------------------------------------------------------------------------------
-  hipEvent_t ev_get() {
-    if (!ev_pool.empty()) {
-      hipEvent_t e = ev_pool.back();
-      ev_pool.pop_back();
-      return e;
-    }
-    hipEvent_t e;
-    hipEventCreate(&e);
+// ---- timers -------------------------------------------------------------------------------
+hipEvent_t pnp_ctx::ev_get() {
+  if (!ev_pool.empty()) {
+    hipEvent_t e = ev_pool.back();
+    ev_pool.pop_back();
     return e;
   }
-  hipEvent_t tb(int cat) {
-    if (!timing) return nullptr;
-    hipEvent_t e = ev_get();
-    hipEventRecord(e, stream);
-    (void)cat;
-    return e;
-  }
-  void te(int cat, hipEvent_t start) {
-    if (!timing || !start) return;
-    hipEvent_t e = ev_get();
-    hipEventRecord(e, stream);
-    ev_pending[cat].push_back({start, e});
-    t_n[cat]++;
-  }
-  void timers_flush() {
-    hipStreamSynchronize(stream);
-    for (int c = 0; c < T_NCAT; c++) {
-      for (auto &pr : ev_pending[c]) {
-        float ms = 0;
-        hipEventElapsedTime(&ms, pr.first, pr.second);
-        t_ms[c] += ms;
-        ev_pool.push_back(pr.first);
-        ev_pool.push_back(pr.second);
-      }
-      ev_pending[c].clear();
+  hipEvent_t e;
+  hipEventCreate(&e);
+  return e;
+}
+
+void pnp_ctx::timers_flush() {
+  hipStreamSynchronize(stream);
+  for (int c = 0; c < T_NCAT; c++) {
+    for (auto &pr : ev_pending[c]) {
+      float ms = 0;
+      hipEventElapsedTime(&ms, pr.first, pr.second);
+      t_ms[c] += ms;
+      ev_pool.push_back(pr.first);
+      ev_pool.push_back(pr.second);
     }
+    ev_pending[c].clear();
   }
+}
 
-  // ---- helpers ------------------------------------------------------------------------------
-  long long nown() const { return (long long)L.n_owned * nf; }
-
-  int halo(double *vec, int nfv) { return halo_on(vec, nfv, stream); }
-
-  int halo_on(double *vec, int nfv, hipStream_t hs) {
-    if (nranks == 1) return PNP_OK;
-    if (lg) return halo_local(vec, nfv);
-    if (host_tr()) return halo_host(vec, nfv);
-    if (L.nbr_ranks.empty()) return PNP_OK;
-    hipEvent_t t0 = hs == stream ? tb(T_HALO) : nullptr;
-    int ns = int(L.send_idx.size());
-    hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, hs);
-    if (e != hipSuccess) return hipfail(e, "halo pack");
-    if (ncclGroupStart() != ncclSuccess) return fail(PNP_E_RCCL, "ncclGroupStart");
-    for (size_t q = 0; q < L.nbr_ranks.size(); q++) {
-      int peer = L.nbr_ranks[q];
-      size_t sc = size_t(L.send_ptr[q + 1] - L.send_ptr[q]) * nfv;
-      size_t rc = size_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
-      if (ncclSend(sendbuf.p + size_t(L.send_ptr[q]) * nfv, sc, ncclDouble, peer, comm, hs) !=
-          ncclSuccess)
-        return fail(PNP_E_RCCL, "ncclSend");
-      if (ncclRecv(vec + (size_t(L.n_owned) + L.recv_ptr[q]) * nfv, rc, ncclDouble, peer, comm,
-                   hs) != ncclSuccess)
-        return fail(PNP_E_RCCL, "ncclRecv");
-    }
-    if (ncclGroupEnd() != ncclSuccess) return fail(PNP_E_RCCL, "ncclGroupEnd");
-    if (t0) te(T_HALO, t0);
-    return PNP_OK;
+int pnp_ctx::halo_on(double *vec, int nfv, hipStream_t hs) {
+  if (nranks == 1) return PNP_OK;
+  if (lg) return halo_local(vec, nfv);
+  if (host_tr()) return halo_host(vec, nfv);
+  if (L.nbr_ranks.empty()) return PNP_OK;
+  hipEvent_t t0 = hs == stream ? tb(T_HALO) : nullptr;
+  int ns = int(L.send_idx.size());
+  hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, hs);
+  if (e != hipSuccess) return hipfail(e, "halo pack");
+  if (ncclGroupStart() != ncclSuccess) return fail(PNP_E_RCCL, "ncclGroupStart");
+  for (size_t q = 0; q < L.nbr_ranks.size(); q++) {
+    int peer = L.nbr_ranks[q];
+    size_t sc = size_t(L.send_ptr[q + 1] - L.send_ptr[q]) * nfv;
+    size_t rc = size_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
+    if (ncclSend(sendbuf.p + size_t(L.send_ptr[q]) * nfv, sc, ncclDouble, peer, comm, hs) !=
+        ncclSuccess)
+      return fail(PNP_E_RCCL, "ncclSend");
+    if (ncclRecv(vec + (size_t(L.n_owned) + L.recv_ptr[q]) * nfv, rc, ncclDouble, peer, comm,
+                 hs) != ncclSuccess)
+      return fail(PNP_E_RCCL, "ncclRecv");
   }
+  if (ncclGroupEnd() != ncclSuccess) return fail(PNP_E_RCCL, "ncclGroupEnd");
+  if (t0) te(T_HALO, t0);
+  return PNP_OK;
+}
 
-  // the operator application on the rows of Lr (dl or one of its block subsets): the SpMV on the
-  // SELL values, or, with the Jacobian held as a linearisation point, the matrix-free kernel
-  hipError_t apply_op(const pnp::DevLayout &Lr, const double *vin, double *yout, int mode,
-                      const double *w, double *parts, int *nparts, hipStream_t s,
-                      const double *w2 = nullptr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-    if (mf_lin)
-      return pnp::launch_jac_apply(Lr, mf_aa, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);
-    return pnp::launch_spmv(Lr, nf, pat, vals.p, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);
-  }
-
-  // halo exchange of vin's ghosts + y = A vin (mode / dots as launch_spmv).  Multi-GPU with the
-  // split layout: the interior blocks (no ghost columns) run while the halo is in flight on
-  // cstream, then the boundary blocks; their partials follow each other, *nsp counts both.
-  int halo_spmv(double *vin, double *yout, int mode, const double *w, const double *w2, int *nsp) {
-    hipError_t e;
-    if (mf_lin) mf_applies++;  // an interior + boundary pair counts once
-    if (!split_spmv) {
-      int rc = halo(vin, nf);
-      if (rc) return rc;
-      // the launch records the timer events itself (the kernel's own duration)
-      hipEvent_t t0 = nullptr, t1 = nullptr;
-      if (timing && L.n_owned > 0) {
-        t0 = ev_get();
-        t1 = ev_get();
-      }
-      e = apply_op(dl, vin, yout, mode, w, partials.p, nsp, stream, w2, t0, t1);
-      if (e != hipSuccess) return hipfail(e, "spmv");
-      if (t1) {
-        ev_pending[T_SPMV].push_back({t0, t1});
-        t_n[T_SPMV]++;
-      }
-      return PNP_OK;
-    }
-    const int kd = mode == 4 ? 3 : (mode == 2 ? 2 : 1);
-    const pnp::DevLayout dl_int = sub_layout(true), dl_bnd = sub_layout(false);
-    int n1 = 0, n2 = 0, rc;
-    if (lg || host_tr()) {  // in-process / host-staged transport: synchronous halo between the halves
-      hipEvent_t t0 = tb(T_SPMV);
-      e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
-      if (e != hipSuccess) return hipfail(e, "spmv interior");
-      te(T_SPMV, t0);
-      if ((rc = halo(vin, nf))) return rc;
-    } else {
-      if ((e = hipEventRecord(ev_ready, stream)) != hipSuccess ||
-          (e = hipStreamWaitEvent(cstream, ev_ready, 0)) != hipSuccess)
-        return hipfail(e, "halo stream order");
-      if ((rc = halo_on(vin, nf, cstream))) return rc;
-      if ((e = hipEventRecord(ev_halo, cstream)) != hipSuccess) return hipfail(e, "halo event");
-      hipEvent_t t0 = tb(T_SPMV);
-      e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
-      if (e != hipSuccess) return hipfail(e, "spmv interior");
-      te(T_SPMV, t0);
-      if ((e = hipStreamWaitEvent(stream, ev_halo, 0)) != hipSuccess)
-        return hipfail(e, "halo wait");
-    }
-    hipEvent_t t1 = tb(T_SPMV);
-    e = apply_op(dl_bnd, vin, yout, mode, w, partials.p + size_t(n1) * kd, &n2, stream, w2);
-    if (e != hipSuccess) return hipfail(e, "spmv boundary");
-    te(T_SPMV, t1);
-    *nsp = n1 + n2;
-    return PNP_OK;
-  }
-
-  // host-staged halo: pack on the device, copy to pinned host memory, the caller's exchange, copy
-  // the received ghosts back (synchronous, on the context's stream)
-  int halo_host(double *vec, int nfv) {
-    hipEvent_t t0 = tb(T_HALO);
-    const int ns = int(L.send_idx.size()), nq = int(L.nbr_ranks.size());
-    const size_t nsend = size_t(ns) * nfv, nrecv = size_t(L.n_ghost) * nfv;
-    hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, stream);
-    if (e == hipSuccess && nsend)
-      e = hipMemcpyAsync(h_send, sendbuf.p, sizeof(double) * nsend, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "halo pack");
-    std::vector<int64_t> soff(nq), scnt(nq), roff(nq), rcnt(nq);
-    for (int q = 0; q < nq; q++) {
-      soff[q] = int64_t(L.send_ptr[q]) * nfv;
-      scnt[q] = int64_t(L.send_ptr[q + 1] - L.send_ptr[q]) * nfv;
-      roff[q] = int64_t(L.recv_ptr[q]) * nfv;
-      rcnt[q] = int64_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
-    }
-    if (ht.exchange(ht.user, nq, L.nbr_ranks.data(), h_send, soff.data(), scnt.data(), h_recv,
-                    roff.data(), rcnt.data()) != 0)
-      return fail(PNP_E_RCCL, "host transport: exchange failed");
-    if (nrecv)
-      e = hipMemcpyAsync(vec + size_t(L.n_owned) * nfv, h_recv, sizeof(double) * nrecv,
-                         hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);  // h_recv is reused by the next call
-    if (e != hipSuccess) return hipfail(e, "halo copy");
-    if (t0) te(T_HALO, t0);
-    return PNP_OK;
-  }
-
-  int halo_local(double *vec, int nfv) {
-    int ns = int(L.send_idx.size());
-    hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "halo pack");
-    lg->barrier();  // every rank has packed
-    for (size_t q = 0; q < L.nbr_ranks.size(); q++) {
-      pnp_ctx *peer = lg->members[L.nbr_ranks[q]];
-      const pnp::LocalLayout &PL = peer->L;
-      size_t k = 0;
-      while (k < PL.nbr_ranks.size() && PL.nbr_ranks[k] != rank) k++;
-      if (k == PL.nbr_ranks.size()) return fail(PNP_E_STATE, "asymmetric halo");
-      size_t cnt = size_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
-      if (cnt != size_t(PL.send_ptr[k + 1] - PL.send_ptr[k]) * nfv)
-        return fail(PNP_E_STATE, "halo size mismatch");
-      e = hipMemcpyAsync(vec + (size_t(L.n_owned) + L.recv_ptr[q]) * nfv,
-                         peer->sendbuf.p + size_t(PL.send_ptr[k]) * nfv, sizeof(double) * cnt,
-                         hipMemcpyDeviceToDevice, stream);
-      if (e != hipSuccess) return hipfail(e, "halo copy");
-    }
-    e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "halo copy");
-    lg->barrier();  // nobody repacks before every copy out of the send buffers is done
-    return PNP_OK;
-  }
-
-  // in-place sum over ranks of k doubles in device memory
-  int allreduce_dev(double *d, int k) {
-    if (!dist) return PNP_OK;
-    if (lg) {
-      std::vector<double> h(k);
-      hipError_t e = hipMemcpyAsync(h.data(), d, sizeof(double) * k, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return hipfail(e, "allreduce");
-      lg->host[rank] = h;
-      lg->barrier();
-      std::vector<double> sum(k, 0.0);
-      for (int r = 0; r < nranks; r++)  // fixed rank order: deterministic
-        for (int j = 0; j < k; j++) sum[j] += lg->host[r][j];
-      lg->barrier();
-      e = hipMemcpyAsync(d, sum.data(), sizeof(double) * k, hipMemcpyHostToDevice, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      return e == hipSuccess ? PNP_OK : hipfail(e, "allreduce");
-    }
-    if (host_tr()) {
-      if (size_t(k) > h_red_n) {
-        if (h_red) hipHostFree(h_red);
-        h_red = nullptr;
-        h_red_n = 0;
-        hipError_t e = hipHostMalloc(&h_red, sizeof(double) * size_t(k));
-        if (e != hipSuccess) return hipfail(e, "allreduce staging");
-        h_red_n = size_t(k);
-      }
-      hipError_t e = hipMemcpyAsync(h_red, d, sizeof(double) * k, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return hipfail(e, "allreduce");
-      if (ht.allreduce_sum(ht.user, h_red, k) != 0)
-        return fail(PNP_E_RCCL, "host transport: allreduce failed");
-      e = hipMemcpyAsync(d, h_red, sizeof(double) * k, hipMemcpyHostToDevice, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      return e == hipSuccess ? PNP_OK : hipfail(e, "allreduce");
-    }
-    ncclResult_t nr = ncclAllReduce(d, d, k, ncclDouble, ncclSum, comm, stream);
-    if (nr != ncclSuccess)
-      return fail(PNP_E_RCCL, std::string("ncclAllReduce: ") + ncclGetErrorString(nr));
-    return PNP_OK;
-  }
-
-  int allreduce_red(int k) {
-    if (!dist) return PNP_OK;
-    hipEvent_t t0 = tb(T_ALLRED);
-    double *red = reinterpret_cast<double *>(reinterpret_cast<char *>(S.p) +
-                                             offsetof(pnp::Scalars, red));
-    int rc = allreduce_dev(red, k);
+// halo exchange of vin's ghosts + y = A vin (mode / dots as launch_spmv).  Multi-GPU with the
+// split layout: the interior blocks (no ghost columns) run while the halo is in flight on
+// cstream, then the boundary blocks; their partials follow each other, *nsp counts both.
+int pnp_ctx::halo_spmv(double *vin, double *yout, int mode, const double *w, const double *w2,
+                       int *nsp) {
+  hipError_t e;
+  if (mf_lin) mf_applies++;  // an interior + boundary pair counts once
+  if (!split_spmv) {
+    int rc = halo(vin, nf);
     if (rc) return rc;
-    te(T_ALLRED, t0);
-    return PNP_OK;
-  }
-
-  // S->red = sum of partials (all ranks), then the derive step of BiCGSTAB stage `stage`
-  int reduce_derive(int np, int k, int stage, bool from2 = false) {
-    hipError_t e;
-    const double *src = from2 ? partials2.p : partials.p;
-    if (!dist) {
-      e = pnp::launch_reduce(src, np, k, S.p, stream, stage, redmw.p);
-      return e == hipSuccess ? PNP_OK : hipfail(e, "reduce");
-    }
-    e = pnp::launch_reduce(src, np, k, S.p, stream, -1, redmw.p);
-    if (e != hipSuccess) return hipfail(e, "reduce");
-    int rc = allreduce_red(k);
-    if (rc) return rc;
-    e = pnp::launch_derive(S.p, stage, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "derive");
-  }
-
-  // S->red[0..ka) = sum of partials (spmv), S->red[ka..) = sum of partials2, all ranks; derive
-  int reduce_derive2(int npa, int ka, int npb, int kb, int stage) {
-    hipError_t e;
-    if (!dist) {
-      e = pnp::launch_reduce2(partials.p, npa, ka, partials2.p, npb, kb, S.p, stream, stage,
-                              redmw.p);
-      return e == hipSuccess ? PNP_OK : hipfail(e, "reduce");
-    }
-    e = pnp::launch_reduce2(partials.p, npa, ka, partials2.p, npb, kb, S.p, stream, -1, redmw.p);
-    if (e != hipSuccess) return hipfail(e, "reduce");
-    int rc = allreduce_red(ka + kb);
-    if (rc) return rc;
-    e = pnp::launch_derive(S.p, stage, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "derive");
-  }
-
-  // norm over owned rows of a vector, synchronous
-  int norm(const double *vec, double &out) {
-    hipEvent_t t0 = tb(T_BLAS);
-    hipError_t e = pnp::launch_dot(nown(), vec, vec, 0, partials.p, stream);
-    if (e == hipSuccess) {
-      // reduce through the scalar block without touching the BiCGSTAB state: use a scratch
-      // Scalars at S.p + 1
-      e = pnp::launch_reduce(partials.p, pnp::blas_nparts(nown()), 1, S.p + 1, stream);
-    }
-    if (e != hipSuccess) return hipfail(e, "norm");
-    te(T_BLAS, t0);
-    if (dist) {
-      double *red = reinterpret_cast<double *>(reinterpret_cast<char *>(S.p + 1) +
-                                               offsetof(pnp::Scalars, red));
-      int rc = allreduce_dev(red, 1);
-      if (rc) return rc;
-    }
-    e = hipMemcpyAsync(hS + 1, S.p + 1, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "norm readback");
-    out = std::sqrt(hS[1].red[0]);
-    return PNP_OK;
-  }
-
-  // external (lexicographic, global) vector -> the internal layout; devptr: `host` is a device
-  // pointer (PNP_DEVICE_PTRS), gathered from directly
-  int upload_ext(const double *host, int nfv, double *dev, bool with_ghosts, bool devptr = false) {
-    size_t ne = size_t(mesh.nv) * nfv;
-    hipError_t e = hipSuccess;
-    if (!devptr)
-      e = hipMemcpyAsync(ext.p, host, sizeof(double) * ne, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess)
-      e = pnp::launch_gather_ext(with_ghosts ? L.n_owned + L.n_ghost : L.n_owned, nfv, mesh.nv,
-                                 d_l2g.p, devptr ? host : ext.p, dev, stream);
-    if (e != hipSuccess) return hipfail(e, "upload");
-    return PNP_OK;
-  }
-
-  // internal -> external; this rank's owned entries are written (devptr: into device memory,
-  // synchronised before return)
-  int download_ext(const double *dev, int nfv, double *host, bool devptr = false) {
-    if (devptr) {
-      hipError_t e = pnp::launch_scatter_ext(L.n_owned, nfv, mesh.nv, d_l2g.p, dev, host, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      return e == hipSuccess ? PNP_OK : hipfail(e, "download");
-    }
-    size_t ne = size_t(mesh.nv) * nfv;
-    hipError_t e = pnp::launch_scatter_ext(L.n_owned, nfv, mesh.nv, d_l2g.p, dev, ext.p, stream);
-    std::vector<double> tmp(ne);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(tmp.data(), ext.p, sizeof(double) * ne, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "download");
-    for (int i = 0; i < L.n_owned; i++) {
-      int g = L.l2g[i];
-      for (int f = 0; f < nfv; f++) host[size_t(f) * mesh.nv + g] = tmp[size_t(f) * mesh.nv + g];
-    }
-    return PNP_OK;
-  }
-
-  int assemble(const double *xdev, int jac) {
-    if (kind < 0) return fail(PNP_E_STATE, "no operator set (pnp_set_operator)");
-    int rc;
-    if (jac && (rc = set_fd(fd_opt != 0))) return rc;
-    // matrix-free (P1, analytic): the Jacobian is the recorded point; only the residual the fused
-    // assembly would also have produced is computed now (Newton's right-hand side)
-    const bool mf = jac && mf_opt && degree == 1 && !fd_mode;
-    if (mf && (rc = mf_record(xdev))) return rc;
-    aa.x = xdev;
-    aa.jac = (fd_mode || mf) ? 0 : jac;
-    aa.r = r.p;
-    aa.cold = after_solve ? 1 : 0;
-    aa.kconst = (aa.jac && asm_kconst()) ? 1 : 0;
-    // the P1 analytic assembly is one launch: it records its own start / end events (the
-    // kernel's duration, as the kernel trace reports it); the other forms take an event pair
-    const bool one = degree == 1 && !(jac && fd_mode);
+    // the launch records the timer events itself (the kernel's own duration)
     hipEvent_t t0 = nullptr, t1 = nullptr;
-    if (timing && one) {
+    if (timing && L.n_owned > 0) {
       t0 = ev_get();
       t1 = ev_get();
-    } else {
-      t0 = tb(T_ASM);
     }
-    hipError_t e;
-    int piped = 0;
-    if (degree > 1)
-      e = pnp::launch_pk_assemble(dl, aa, pkd, jac ? (fd_mode ? 2 : 1) : 0, stream);
-    else
-      e = pnp::launch_assemble(dl, aa, stream, t1 ? t0 : nullptr, t1, &piped);
-    if (e == hipSuccess && jac && fd_mode && degree == 1)
-      e = pnp::launch_fd_jacobian(dl, aa, nf, pat, fd_ne, fd_etri.p, fd_rptr.p, fd_cdata.p,
-                                  fd_jel.p, stream);
-    if (e != hipSuccess) {
-      if (jac && !mf) vals_const_valid = false;
-      return hipfail(e, "assemble");
-    }
-    if (jac && !mf) asm_wrote(aa.kconst != 0, degree == 1 && !fd_mode);
-    asm_piped += piped;
+    e = apply_op(dl, vin, yout, mode, w, partials.p, nsp, stream, w2, t0, t1);
+    if (e != hipSuccess) return hipfail(e, "spmv");
     if (t1) {
-      ev_pending[T_ASM].push_back({t0, t1});
-      t_n[T_ASM]++;
-    } else {
-      te(T_ASM, t0);
-    }
-    if (jac) {
-      assembled = true;
-      lu_valid = false;
-      split_of = 0;
-      amg_valid = false;
-      csr_vals_valid = false;
-      after_solve = false;
-      mf_lin = vals_stale = mf;
-      mf_diag_valid = false;
-      if (!mf) value_assemblies++;
+      ev_pending[T_SPMV].push_back({t0, t1});
+      t_n[T_SPMV]++;
     }
     return PNP_OK;
   }
-
-  // the linearisation point of a matrix-free Jacobian: the state with its ghosts in a buffer of
-  // its own (a later residual overwrites x) and the operator's arguments as they are now
-  int mf_record(const double *xdev) {
-    const size_t nl = size_t(dl.n_local) * 3;
-    hipError_t e = hipSuccess;
-    if (mf_x.n < nl) e = mf_x.alloc(std::max<size_t>(1, nl));
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(mf_x.p, xdev, sizeof(double) * size_t(dl.n_local) * nf,
-                         hipMemcpyDeviceToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "linearisation point");
-    mf_aa = aa;
-    mf_aa.x = mf_x.p;
-    mf_aa.jac = 1;
-    mf_aa.r = nullptr;
-    mf_aa.cold = 0;
-    return PNP_OK;
+  const int kd = mode == 4 ? 3 : (mode == 2 ? 2 : 1);
+  const pnp::DevLayout dl_int = sub_layout(true), dl_bnd = sub_layout(false);
+  int n1 = 0, n2 = 0, rc;
+  if (lg || host_tr()) {  // in-process / host-staged transport: synchronous halo between the halves
+    hipEvent_t t0 = tb(T_SPMV);
+    e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
+    if (e != hipSuccess) return hipfail(e, "spmv interior");
+    te(T_SPMV, t0);
+    if ((rc = halo(vin, nf))) return rc;
+  } else {
+    if ((e = hipEventRecord(ev_ready, stream)) != hipSuccess ||
+        (e = hipStreamWaitEvent(cstream, ev_ready, 0)) != hipSuccess)
+      return hipfail(e, "halo stream order");
+    if ((rc = halo_on(vin, nf, cstream))) return rc;
+    if ((e = hipEventRecord(ev_halo, cstream)) != hipSuccess) return hipfail(e, "halo event");
+    hipEvent_t t0 = tb(T_SPMV);
+    e = apply_op(dl_int, vin, yout, mode, w, partials.p, &n1, stream, w2);
+    if (e != hipSuccess) return hipfail(e, "spmv interior");
+    te(T_SPMV, t0);
+    if ((e = hipStreamWaitEvent(stream, ev_halo, 0)) != hipSuccess)
+      return hipfail(e, "halo wait");
   }
+  hipEvent_t t1 = tb(T_SPMV);
+  e = apply_op(dl_bnd, vin, yout, mode, w, partials.p + size_t(n1) * kd, &n2, stream, w2);
+  if (e != hipSuccess) return hipfail(e, "spmv boundary");
+  te(T_SPMV, t1);
+  *nsp = n1 + n2;
+  return PNP_OK;
+}
 
-  // the SELL values of a Jacobian held as a linearisation point, for whoever reads vals: the
-  // ordinary fused assembly at the point, once (its residual goes to a scratch vector)
-  int ensure_values() {
-    if (!mf_lin || !vals_stale) return PNP_OK;
-    const size_t no = size_t(L.n_owned) * 3;
-    hipError_t e = hipSuccess;
-    if (mf_r.n < no) e = mf_r.alloc(std::max<size_t>(1, no));
-    if (e != hipSuccess) return hipfail(e, "assemble at the linearisation point");
-    pnp::AsmArgs fa = mf_aa;
-    fa.r = mf_r.p;
-    fa.vals = vals.p;
-    fa.cold = after_solve ? 1 : 0;
-    fa.kconst = asm_kconst() ? 1 : 0;
-    hipEvent_t t0 = tb(T_ASM);
-    int piped = 0;
-    e = pnp::launch_assemble(dl, fa, stream, nullptr, nullptr, &piped);
-    if (e != hipSuccess) {
-      vals_const_valid = false;
-      return hipfail(e, "assemble at the linearisation point");
+// host-staged halo: pack on the device, copy to pinned host memory, the caller's exchange, copy
+// the received ghosts back (synchronous, on the context's stream)
+int pnp_ctx::halo_host(double *vec, int nfv) {
+  hipEvent_t t0 = tb(T_HALO);
+  const int ns = int(L.send_idx.size()), nq = int(L.nbr_ranks.size());
+  const size_t nsend = size_t(ns) * nfv, nrecv = size_t(L.n_ghost) * nfv;
+  hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, stream);
+  if (e == hipSuccess && nsend)
+    e = hipMemcpyAsync(h_send, sendbuf.p, sizeof(double) * nsend, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "halo pack");
+  std::vector<int64_t> soff(nq), scnt(nq), roff(nq), rcnt(nq);
+  for (int q = 0; q < nq; q++) {
+    soff[q] = int64_t(L.send_ptr[q]) * nfv;
+    scnt[q] = int64_t(L.send_ptr[q + 1] - L.send_ptr[q]) * nfv;
+    roff[q] = int64_t(L.recv_ptr[q]) * nfv;
+    rcnt[q] = int64_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
+  }
+  if (ht.exchange(ht.user, nq, L.nbr_ranks.data(), h_send, soff.data(), scnt.data(), h_recv,
+                  roff.data(), rcnt.data()) != 0)
+    return fail(PNP_E_RCCL, "host transport: exchange failed");
+  if (nrecv)
+    e = hipMemcpyAsync(vec + size_t(L.n_owned) * nfv, h_recv, sizeof(double) * nrecv,
+                       hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);  // h_recv is reused by the next call
+  if (e != hipSuccess) return hipfail(e, "halo copy");
+  if (t0) te(T_HALO, t0);
+  return PNP_OK;
+}
+
+int pnp_ctx::halo_local(double *vec, int nfv) {
+  int ns = int(L.send_idx.size());
+  hipError_t e = pnp::launch_pack(ns, nfv, d_send_idx.p, vec, sendbuf.p, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "halo pack");
+  lg->barrier();  // every rank has packed
+  for (size_t q = 0; q < L.nbr_ranks.size(); q++) {
+    pnp_ctx *peer = lg->members[L.nbr_ranks[q]];
+    const pnp::LocalLayout &PL = peer->L;
+    size_t k = 0;
+    while (k < PL.nbr_ranks.size() && PL.nbr_ranks[k] != rank) k++;
+    if (k == PL.nbr_ranks.size()) return fail(PNP_E_STATE, "asymmetric halo");
+    size_t cnt = size_t(L.recv_ptr[q + 1] - L.recv_ptr[q]) * nfv;
+    if (cnt != size_t(PL.send_ptr[k + 1] - PL.send_ptr[k]) * nfv)
+      return fail(PNP_E_STATE, "halo size mismatch");
+    e = hipMemcpyAsync(vec + (size_t(L.n_owned) + L.recv_ptr[q]) * nfv,
+                       peer->sendbuf.p + size_t(PL.send_ptr[k]) * nfv, sizeof(double) * cnt,
+                       hipMemcpyDeviceToDevice, stream);
+    if (e != hipSuccess) return hipfail(e, "halo copy");
+  }
+  e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "halo copy");
+  lg->barrier();  // nobody repacks before every copy out of the send buffers is done
+  return PNP_OK;
+}
+
+// in-place sum over ranks of k doubles in device memory
+int pnp_ctx::allreduce_dev(double *d, int k) {
+  if (!dist) return PNP_OK;
+  if (lg) {
+    std::vector<double> h(k);
+    hipError_t e = hipMemcpyAsync(h.data(), d, sizeof(double) * k, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "allreduce");
+    lg->host[rank] = h;
+    lg->barrier();
+    std::vector<double> sum(k, 0.0);
+    for (int r = 0; r < nranks; r++)  // fixed rank order: deterministic
+      for (int j = 0; j < k; j++) sum[j] += lg->host[r][j];
+    lg->barrier();
+    e = hipMemcpyAsync(d, sum.data(), sizeof(double) * k, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "allreduce");
+  }
+  if (host_tr()) {
+    if (size_t(k) > h_red_n) {
+      if (h_red) hipHostFree(h_red);
+      h_red = nullptr;
+      h_red_n = 0;
+      hipError_t e = hipHostMalloc(&h_red, sizeof(double) * size_t(k));
+      if (e != hipSuccess) return hipfail(e, "allreduce staging");
+      h_red_n = size_t(k);
     }
-    asm_wrote(fa.kconst != 0, true);
-    asm_piped += piped;
+    hipError_t e = hipMemcpyAsync(h_red, d, sizeof(double) * k, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "allreduce");
+    if (ht.allreduce_sum(ht.user, h_red, k) != 0)
+      return fail(PNP_E_RCCL, "host transport: allreduce failed");
+    e = hipMemcpyAsync(d, h_red, sizeof(double) * k, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "allreduce");
+  }
+  ncclResult_t nr = ncclAllReduce(d, d, k, ncclDouble, ncclSum, comm, stream);
+  if (nr != ncclSuccess)
+    return fail(PNP_E_RCCL, std::string("ncclAllReduce: ") + ncclGetErrorString(nr));
+  return PNP_OK;
+}
+
+int pnp_ctx::allreduce_red(int k) {
+  if (!dist) return PNP_OK;
+  hipEvent_t t0 = tb(T_ALLRED);
+  double *red = reinterpret_cast<double *>(reinterpret_cast<char *>(S.p) +
+                                           offsetof(pnp::Scalars, red));
+  int rc = allreduce_dev(red, k);
+  if (rc) return rc;
+  te(T_ALLRED, t0);
+  return PNP_OK;
+}
+
+// S->red = sum of partials (all ranks), then the derive step of BiCGSTAB stage `stage`
+int pnp_ctx::reduce_derive(int np, int k, int stage, bool from2) {
+  hipError_t e;
+  const double *src = from2 ? partials2.p : partials.p;
+  if (!dist) {
+    e = pnp::launch_reduce(src, np, k, S.p, stream, stage, redmw.p);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "reduce");
+  }
+  e = pnp::launch_reduce(src, np, k, S.p, stream, -1, redmw.p);
+  if (e != hipSuccess) return hipfail(e, "reduce");
+  int rc = allreduce_red(k);
+  if (rc) return rc;
+  e = pnp::launch_derive(S.p, stage, stream);
+  return e == hipSuccess ? PNP_OK : hipfail(e, "derive");
+}
+
+// S->red[0..ka) = sum of partials (spmv), S->red[ka..) = sum of partials2, all ranks; derive
+int pnp_ctx::reduce_derive2(int npa, int ka, int npb, int kb, int stage) {
+  hipError_t e;
+  if (!dist) {
+    e = pnp::launch_reduce2(partials.p, npa, ka, partials2.p, npb, kb, S.p, stream, stage,
+                            redmw.p);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "reduce");
+  }
+  e = pnp::launch_reduce2(partials.p, npa, ka, partials2.p, npb, kb, S.p, stream, -1, redmw.p);
+  if (e != hipSuccess) return hipfail(e, "reduce");
+  int rc = allreduce_red(ka + kb);
+  if (rc) return rc;
+  e = pnp::launch_derive(S.p, stage, stream);
+  return e == hipSuccess ? PNP_OK : hipfail(e, "derive");
+}
+
+// norm over owned rows of a vector, synchronous
+int pnp_ctx::norm(const double *vec, double &out) {
+  hipEvent_t t0 = tb(T_BLAS);
+  hipError_t e = pnp::launch_dot(nown(), vec, vec, 0, partials.p, stream);
+  if (e == hipSuccess) {
+    // reduce through the scalar block without touching the BiCGSTAB state: use a scratch
+    // Scalars at S.p + 1
+    e = pnp::launch_reduce(partials.p, pnp::blas_nparts(nown()), 1, S.p + 1, stream);
+  }
+  if (e != hipSuccess) return hipfail(e, "norm");
+  te(T_BLAS, t0);
+  if (dist) {
+    double *red = reinterpret_cast<double *>(reinterpret_cast<char *>(S.p + 1) +
+                                             offsetof(pnp::Scalars, red));
+    int rc = allreduce_dev(red, 1);
+    if (rc) return rc;
+  }
+  if (int rc = poll(hS + 1, S.p + 1, sizeof(pnp::Scalars), "norm readback")) return rc;
+  out = std::sqrt(hS[1].red[0]);
+  return PNP_OK;
+}
+
+// external (lexicographic, global) vector -> the internal layout; devptr: `host` is a device
+// pointer (PNP_DEVICE_PTRS), gathered from directly
+int pnp_ctx::upload_ext(const double *host, int nfv, double *dev, bool with_ghosts, bool devptr) {
+  size_t ne = size_t(mesh.nv) * nfv;
+  hipError_t e = hipSuccess;
+  if (!devptr)
+    e = hipMemcpyAsync(ext.p, host, sizeof(double) * ne, hipMemcpyHostToDevice, stream);
+  if (e == hipSuccess)
+    e = pnp::launch_gather_ext(with_ghosts ? L.n_owned + L.n_ghost : L.n_owned, nfv, mesh.nv,
+                               d_l2g.p, devptr ? host : ext.p, dev, stream);
+  if (e != hipSuccess) return hipfail(e, "upload");
+  return PNP_OK;
+}
+
+// internal -> external; this rank's owned entries are written (devptr: into device memory,
+// synchronised before return)
+int pnp_ctx::download_ext(const double *dev, int nfv, double *host, bool devptr) {
+  if (devptr) {
+    hipError_t e = pnp::launch_scatter_ext(L.n_owned, nfv, mesh.nv, d_l2g.p, dev, host, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    return e == hipSuccess ? PNP_OK : hipfail(e, "download");
+  }
+  size_t ne = size_t(mesh.nv) * nfv;
+  hipError_t e = pnp::launch_scatter_ext(L.n_owned, nfv, mesh.nv, d_l2g.p, dev, ext.p, stream);
+  std::vector<double> tmp(ne);
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(tmp.data(), ext.p, sizeof(double) * ne, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "download");
+  for (int i = 0; i < L.n_owned; i++) {
+    int g = L.l2g[i];
+    for (int f = 0; f < nfv; f++) host[size_t(f) * mesh.nv + g] = tmp[size_t(f) * mesh.nv + g];
+  }
+  return PNP_OK;
+}
+
+int pnp_ctx::assemble(const double *xdev, int jac) {
+  if (kind < 0) return fail(PNP_E_STATE, "no operator set (pnp_set_operator)");
+  int rc;
+  if (jac && (rc = set_fd(fd_opt != 0))) return rc;
+  // matrix-free (P1, analytic): the Jacobian is the recorded point; only the residual the fused
+  // assembly would also have produced is computed now (Newton's right-hand side)
+  const bool mf = jac && mf_opt && degree == 1 && !fd_mode;
+  if (mf && (rc = mf_record(xdev))) return rc;
+  aa.x = xdev;
+  aa.jac = (fd_mode || mf) ? 0 : jac;
+  aa.r = r.p;
+  aa.cold = after_solve ? 1 : 0;
+  aa.kconst = (aa.jac && asm_kconst()) ? 1 : 0;
+  // the P1 analytic assembly is one launch: it records its own start / end events (the
+  // kernel's duration, as the kernel trace reports it); the other forms take an event pair
+  const bool one = degree == 1 && !(jac && fd_mode);
+  hipEvent_t t0 = nullptr, t1 = nullptr;
+  if (timing && one) {
+    t0 = ev_get();
+    t1 = ev_get();
+  } else {
+    t0 = tb(T_ASM);
+  }
+  hipError_t e;
+  int piped = 0;
+  if (degree > 1)
+    e = pnp::launch_pk_assemble(dl, aa, pkd, jac ? (fd_mode ? 2 : 1) : 0, stream);
+  else
+    e = pnp::launch_assemble(dl, aa, stream, t1 ? t0 : nullptr, t1, &piped);
+  if (e == hipSuccess && jac && fd_mode && degree == 1)
+    e = pnp::launch_fd_jacobian(dl, aa, nf, pat, fd_ne, fd_etri.p, fd_rptr.p, fd_cdata.p,
+                                fd_jel.p, stream);
+  if (e != hipSuccess) {
+    if (jac && !mf) vals_const_valid = false;
+    return hipfail(e, "assemble");
+  }
+  if (jac && !mf) asm_wrote(aa.kconst != 0, degree == 1 && !fd_mode);
+  asm_piped += piped;
+  if (t1) {
+    ev_pending[T_ASM].push_back({t0, t1});
+    t_n[T_ASM]++;
+  } else {
     te(T_ASM, t0);
-    vals_stale = false;
-    value_assemblies++;
-    return PNP_OK;
   }
+  if (jac) {
+    assembled = true;
+    lu_valid = false;
+    split_of = 0;
+    amg_valid = false;
+    csr_vals_valid = false;
+    after_solve = false;
+    mf_lin = vals_stale = mf;
+    mf_diag_valid = false;
+    if (!mf) value_assemblies++;
+  }
+  return PNP_OK;
+}
 
-  // Jacobi on a matrix-free Jacobian whose values were never needed: its diagonal blocks alone
-  int jacobi_prepare() {
-    if (!mf_lin || !vals_stale || mf_diag_valid) return PNP_OK;
-    hipError_t e = hipSuccess;
-    if (!mf_choff.p) {
-      std::vector<int> co(size_t(L.nchunks) + 1);
-      for (size_t c = 0; c < co.size(); c++) co[c] = int(c) * pnp::kRows;
-      int rc = upv(mf_choff, co, "diagonal layout");
-      if (rc) return rc;
-      e = mf_diag.alloc(std::max<size_t>(1, size_t(L.nchunks) * pnp::kRows * 6));
+// the linearisation point of a matrix-free Jacobian: the state with its ghosts in a buffer of
+// its own (a later residual overwrites x) and the operator's arguments as they are now
+int pnp_ctx::mf_record(const double *xdev) {
+  const size_t nl = size_t(dl.n_local) * 3;
+  hipError_t e = hipSuccess;
+  if (mf_x.n < nl) e = mf_x.alloc(std::max<size_t>(1, nl));
+  if (e == hipSuccess)
+    e = hipMemcpyAsync(mf_x.p, xdev, sizeof(double) * size_t(dl.n_local) * nf,
+                       hipMemcpyDeviceToDevice, stream);
+  if (e != hipSuccess) return hipfail(e, "linearisation point");
+  mf_aa = aa;
+  mf_aa.x = mf_x.p;
+  mf_aa.jac = 1;
+  mf_aa.r = nullptr;
+  mf_aa.cold = 0;
+  return PNP_OK;
+}
+
+// the SELL values of a Jacobian held as a linearisation point, for whoever reads vals: the
+// ordinary fused assembly at the point, once (its residual goes to a scratch vector)
+int pnp_ctx::ensure_values() {
+  if (!mf_lin || !vals_stale) return PNP_OK;
+  const size_t no = size_t(L.n_owned) * 3;
+  hipError_t e = hipSuccess;
+  if (mf_r.n < no) e = mf_r.alloc(std::max<size_t>(1, no));
+  if (e != hipSuccess) return hipfail(e, "assemble at the linearisation point");
+  pnp::AsmArgs fa = mf_aa;
+  fa.r = mf_r.p;
+  fa.vals = vals.p;
+  fa.cold = after_solve ? 1 : 0;
+  fa.kconst = asm_kconst() ? 1 : 0;
+  hipEvent_t t0 = tb(T_ASM);
+  int piped = 0;
+  e = pnp::launch_assemble(dl, fa, stream, nullptr, nullptr, &piped);
+  if (e != hipSuccess) {
+    vals_const_valid = false;
+    return hipfail(e, "assemble at the linearisation point");
+  }
+  asm_wrote(fa.kconst != 0, true);
+  asm_piped += piped;
+  te(T_ASM, t0);
+  vals_stale = false;
+  value_assemblies++;
+  return PNP_OK;
+}
+
+// Jacobi on a matrix-free Jacobian whose values were never needed: its diagonal blocks alone
+int pnp_ctx::jacobi_prepare() {
+  if (!mf_lin || !vals_stale || mf_diag_valid) return PNP_OK;
+  hipError_t e = hipSuccess;
+  if (!mf_choff.p) {
+    std::vector<int> co(size_t(L.nchunks) + 1);
+    for (size_t c = 0; c < co.size(); c++) co[c] = int(c) * pnp::kRows;
+    int rc = upv(mf_choff, co, "diagonal layout");
+    if (rc) return rc;
+    e = mf_diag.alloc(std::max<size_t>(1, size_t(L.nchunks) * pnp::kRows * 6));
+  }
+  if (e == hipSuccess) e = pnp::launch_jac_diag(dl, mf_aa, mf_diag.p, stream);
+  if (e != hipSuccess) return hipfail(e, "jacobi diagonal");
+  mf_diag_valid = true;
+  return PNP_OK;
+}
+
+// structure of the external-layout CSR view of the current block pattern (host, once per
+// pattern): rows f*nv + g of the owned vertices, columns sorted; per entry the source block
+// (row << 6 | slot) and the value's index in the block pattern.  Also the natural-order SSOR
+// level schedule over these rows.
+int pnp_ctx::csr_structure() {
+  const int nv = mesh.nv, mask = pat & 0x1FF;
+  if (csr_pat == mask && csr_nf == nf) return PNP_OK;
+  // the BiCGSTAB block graphs captured with SSOR_NATURAL hold csr_val, nat_d / nat_v and the level
+  // buffers, all rebuilt below: drop every graph (bumps graph_epoch, part of GraphKey)
+  graphs_clear();
+  const int n = nf * nv;
+  std::vector<int> cnt(n + 1, 0);
+  for (int i = 0; i < L.n_owned; i++) {
+    const int len = pnp::meta_len(L.rowmeta[i]);
+    for (int f = 0; f < nf; f++) {
+      int k = 0;
+      for (int g = 0; g < nf; g++) k += pnp::pat_index(mask, f, g) >= 0;
+      cnt[f * nv + L.l2g[i] + 1] += k * len;
     }
-    if (e == hipSuccess) e = pnp::launch_jac_diag(dl, mf_aa, mf_diag.p, stream);
-    if (e != hipSuccess) return hipfail(e, "jacobi diagonal");
-    mf_diag_valid = true;
-    return PNP_OK;
   }
-
-  // structure of the external-layout CSR view of the current block pattern (host, once per
-  // pattern): rows f*nv + g of the owned vertices, columns sorted; per entry the source block
-  // (row << 6 | slot) and the value's index in the block pattern.  Also the natural-order SSOR
-  // level schedule over these rows.
-  int csr_structure() {
-    const int nv = mesh.nv, mask = pat & 0x1FF;
-    if (csr_pat == mask && csr_nf == nf) return PNP_OK;
-    // the BiCGSTAB block graphs captured with SSOR_NATURAL hold csr_val, nat_d / nat_v and the level
-    // buffers, all rebuilt below: drop every graph (bumps graph_epoch, part of GraphKey)
-    graphs_clear();
-    const int n = nf * nv;
-    std::vector<int> cnt(n + 1, 0);
-    for (int i = 0; i < L.n_owned; i++) {
-      const int len = pnp::meta_len(L.rowmeta[i]);
-      for (int f = 0; f < nf; f++) {
-        int k = 0;
-        for (int g = 0; g < nf; g++) k += pnp::pat_index(mask, f, g) >= 0;
-        cnt[f * nv + L.l2g[i] + 1] += k * len;
+  for (int i = 0; i < n; i++) cnt[i + 1] += cnt[i];
+  const long long nnz = cnt[n];
+  std::vector<int> col(nnz), src(nnz);
+  std::vector<unsigned char> vid(nnz);
+  struct E {
+    int col, src;
+    unsigned char v;
+  };
+  std::vector<E> tmp;
+  for (int i = 0; i < L.n_owned; i++) {
+    const int chunk = i / pnp::kRows, lane = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
+    for (int f = 0; f < nf; f++) {
+      tmp.clear();
+      for (int sl = 0; sl < len; sl++) {
+        const int j = L.colidx[size_t(L.chunk_off[chunk]) + size_t(sl) * pnp::kRows + lane];
+        for (int g = 0; g < nf; g++) {
+          const int v = pnp::pat_index(mask, f, g);
+          if (v >= 0) tmp.push_back({g * nv + L.l2g[j], i << 6 | sl, (unsigned char)v});
+        }
+      }
+      std::sort(tmp.begin(), tmp.end(), [](const E &a, const E &b) { return a.col < b.col; });
+      long long q = cnt[f * nv + L.l2g[i]];
+      for (const E &e : tmp) {
+        col[q] = e.col;
+        src[q] = e.src;
+        vid[q] = e.v;
+        q++;
       }
     }
-    for (int i = 0; i < n; i++) cnt[i + 1] += cnt[i];
-    const long long nnz = cnt[n];
-    std::vector<int> col(nnz), src(nnz);
-    std::vector<unsigned char> vid(nnz);
-    struct E {
-      int col, src;
-      unsigned char v;
-    };
-    std::vector<E> tmp;
-    for (int i = 0; i < L.n_owned; i++) {
-      const int chunk = i / pnp::kRows, lane = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
-      for (int f = 0; f < nf; f++) {
-        tmp.clear();
-        for (int sl = 0; sl < len; sl++) {
-          const int j = L.colidx[size_t(L.chunk_off[chunk]) + size_t(sl) * pnp::kRows + lane];
-          for (int g = 0; g < nf; g++) {
-            const int v = pnp::pat_index(mask, f, g);
-            if (v >= 0) tmp.push_back({g * nv + L.l2g[j], i << 6 | sl, (unsigned char)v});
-          }
-        }
-        std::sort(tmp.begin(), tmp.end(), [](const E &a, const E &b) { return a.col < b.col; });
-        long long q = cnt[f * nv + L.l2g[i]];
-        for (const E &e : tmp) {
-          col[q] = e.col;
-          src[q] = e.src;
-          vid[q] = e.v;
-          q++;
+  }
+  int rc;
+  if ((rc = upv(csr_rowptr, cnt, "csr rowptr")) || (rc = upv(csr_col, col, "csr col")) ||
+      (rc = upv(csr_src, src, "csr src")) || (rc = upv(csr_vidx, vid, "csr vidx")))
+    return rc;
+  hipError_t e = csr_val.alloc(std::max<long long>(1, nnz));
+  if (e != hipSuccess) return hipfail(e, "csr values");
+  // natural-order SSOR schedule.  A row R must run after every row it shares a matrix entry with
+  // (A_RC or A_CR stored) that comes before it in the sweep, and before every such later row:
+  // level(R) = 1 + max level of its earlier partners, computed in sweep order with the partners
+  // of the transposed entries pushed forward.  Rows of other ranks' vertices are empty and stay
+  // out (their columns read zero).
+  auto empty = [&](int R) { return cnt[R] == cnt[R + 1]; };
+  std::vector<int> diag(n, -1);
+  for (int R = 0; R < n; R++)
+    for (int k = cnt[R]; k < cnt[R + 1]; k++)
+      if (col[k] == R) diag[R] = k;
+  for (int R = 0; R < n; R++)
+    if (!empty(R) && diag[R] < 0) return fail(PNP_E_STATE, "natural SSOR: row without diagonal");
+  if ((rc = upv(csr_diag, diag, "csr diagonal"))) return rc;
+  // the dataflow sweeps keep their results and operands in the external (lexicographic) layout
+  // R = f * nv + g, which is local in the sweep order (indexing them by internal position
+  // instead made the PNP heads 10-16 % slower, profiles/r05/nat_split_r5e.txt), but read d at
+  // the row's INTERNAL position g2l[g] * nf + f (info.w / rec.w), so that the preconditioner's
+  // input needs no scatter into an external copy (PNP config 3: 20 us per application,
+  // profiles/r05/nat_split_r5d.txt); the result is gathered out of vb afterwards
+  auto P = [&](int R) { return L.g2l[R % nv] * nf + R / nv; };
+  // NatSweep::info packs a row's entry count and its diagonal's offset into one int as
+  // len | offset << 8 (the kernels decode len & 255): at most 255 entries per row (P1 PNP rows
+  // have <= 3 * 21); a wider pattern would corrupt both, so refuse it here
+  for (int R = 0; R < n; R++)
+    if (cnt[R + 1] - cnt[R] > 255)
+      return fail(PNP_E_STATE, "natural SSOR: a row has more than 255 CSR entries (row " +
+                                   std::to_string(R) + ")");
+  auto schedule = [&](bool fwd, NatDir &W) -> int {
+    std::vector<int> &lptr = W.lptr;
+    std::vector<int> lev(n, -1), push(n, 0);
+    int nlev = 0;
+    for (int s = 0; s < n; s++) {
+      const int R = fwd ? s : n - 1 - s;
+      if (empty(R)) continue;
+      int l = push[R];
+      for (int k = cnt[R]; k < cnt[R + 1]; k++) {
+        const int C = col[k];
+        if (C != R && (fwd ? C < R : C > R) && !empty(C)) l = std::max(l, lev[C] + 1);
+      }
+      lev[R] = l;
+      nlev = std::max(nlev, l + 1);
+      for (int k = cnt[R]; k < cnt[R + 1]; k++) {
+        const int C = col[k];
+        if (C != R && (fwd ? C > R : C < R) && !empty(C)) push[C] = std::max(push[C], l + 1);
+      }
+    }
+    lptr.assign(nlev + 1, 0);
+    for (int R = 0; R < n; R++)
+      if (lev[R] >= 0) lptr[lev[R] + 1]++;
+    for (int l = 0; l < nlev; l++) lptr[l + 1] += lptr[l];
+    std::vector<int> fill(lptr.begin(), lptr.end() - 1), rl(std::max(1, lptr[nlev]));
+    for (int R = 0; R < n; R++)
+      if (lev[R] >= 0) rl[fill[lev[R]]++] = R;
+    // per level an ELL of its rows' entries (CSR order), width = its longest row, padding
+    // slots with value index -1, stored unit by unit: the level's rows in groups of UR (the
+    // dataflow units), each group's entries k-major, entry k of the group's row r at
+    // (group * width + k) * UR + r.  A unit's slots are then one contiguous run of lines that no
+    // other unit touches (column-major over the whole level, 4 units shared every line of a
+    // slot, fetched once per XCD that ran one of them: the PNP head missed L2 ~16.7 M times per
+    // launch, profiles/r05/nat_pmc_mem_r5a.json)
+    const int UR = pnp::ssor_natural_unit_rows();
+    std::vector<int4> info(std::max(1, lptr[nlev]));
+    std::vector<int> lwidth(nlev, 0);
+    W.eoff.assign(nlev + 1, 0);
+    for (int l = 0; l < nlev; l++) {
+      int w = 0;
+      for (int t = lptr[l]; t < lptr[l + 1]; t++) w = std::max(w, cnt[rl[t] + 1] - cnt[rl[t]]);
+      lwidth[l] = w;
+      W.eoff[l + 1] = W.eoff[l] + (long long)w * UR * ((lptr[l + 1] - lptr[l] + UR - 1) / UR);
+    }
+    // operand codes (NatSweep): the forward sweep reads the new value of an earlier row (C < R)
+    // and zero for the row itself and later rows; the backward sweep reads the forward value of
+    // rows C <= R and the new backward value of later rows; rows of other ranks read zero
+    std::vector<int> ecol(std::max<long long>(1, W.eoff[nlev]), -1);
+    for (int l = 0; l < nlev; l++) {
+      for (int t = lptr[l]; t < lptr[l + 1]; t++) {
+        const int R = rl[t], len = cnt[R + 1] - cnt[R], tl = t - lptr[l];
+        info[t] = make_int4(R, len | (diag[R] - cnt[R]) << 8, cnt[R], P(R));
+        for (int k = 0; k < len; k++) {
+          const size_t q =
+              size_t(W.eoff[l]) + (size_t(tl / UR) * lwidth[l] + k) * UR + size_t(tl % UR);
+          const int C = col[cnt[R] + k];
+          ecol[q] = empty(C) ? -1 : fwd ? (C < R ? C : -1) : (C <= R ? C : -(C + 2));
         }
       }
     }
-    int rc;
-    if ((rc = upv(csr_rowptr, cnt, "csr rowptr")) || (rc = upv(csr_col, col, "csr col")) ||
-        (rc = upv(csr_src, src, "csr src")) || (rc = upv(csr_vidx, vid, "csr vidx")))
-      return rc;
-    hipError_t e = csr_val.alloc(std::max<long long>(1, nnz));
-    if (e != hipSuccess) return hipfail(e, "csr values");
-    // natural-order SSOR schedule.  A row R must run after every row it shares a matrix entry with
-    // (A_RC or A_CR stored) that comes before it in the sweep, and before every such later row:
-    // level(R) = 1 + max level of its earlier partners, computed in sweep order with the partners
-    // of the transposed entries pushed forward.  Rows of other ranks' vertices are empty and stay
-    // out (their columns read zero).
-    auto empty = [&](int R) { return cnt[R] == cnt[R + 1]; };
-    std::vector<int> diag(n, -1);
-    for (int R = 0; R < n; R++)
-      for (int k = cnt[R]; k < cnt[R + 1]; k++)
-        if (col[k] == R) diag[R] = k;
-    for (int R = 0; R < n; R++)
-      if (!empty(R) && diag[R] < 0) return fail(PNP_E_STATE, "natural SSOR: row without diagonal");
-    if ((rc = upv(csr_diag, diag, "csr diagonal"))) return rc;
-    // the dataflow sweeps keep their results and operands in the external (lexicographic) layout
-    // R = f * nv + g, which is local in the sweep order (indexing them by internal position
-    // instead made the PNP heads 10-16 % slower, profiles/r05/nat_split_r5e.txt), but read d at
-    // the row's INTERNAL position g2l[g] * nf + f (info.w / rec.w), so that the preconditioner's
-    // input needs no scatter into an external copy (PNP config 3: 20 us per application,
-    // profiles/r05/nat_split_r5d.txt); the result is gathered out of vb afterwards
-    auto P = [&](int R) { return L.g2l[R % nv] * nf + R / nv; };
-    // NatSweep::info packs a row's entry count and its diagonal's offset into one int as
-    // len | offset << 8 (the kernels decode len & 255): at most 255 entries per row (P1 PNP rows
-    // have <= 3 * 21); a wider pattern would corrupt both, so refuse it here
-    for (int R = 0; R < n; R++)
-      if (cnt[R + 1] - cnt[R] > 255)
-        return fail(PNP_E_STATE, "natural SSOR: a row has more than 255 CSR entries (row " +
-                                     std::to_string(R) + ")");
-    auto schedule = [&](bool fwd, NatDir &W) -> int {
-      std::vector<int> &lptr = W.lptr;
-      std::vector<int> lev(n, -1), push(n, 0);
-      int nlev = 0;
-      for (int s = 0; s < n; s++) {
-        const int R = fwd ? s : n - 1 - s;
-        if (empty(R)) continue;
-        int l = push[R];
+    // dataflow units for the one-launch sweep: up to ssor_natural_unit_rows() consecutive rows of one level,
+    // {first sweep position, rows | width << 8, the ELL stride between a row's entries (UR), ELL
+    // index of the unit's first row}; forward units in level order, then backward units in level
+    // order.  The
+    // sweep's tail -- the levels from the last one wider than PNP_NAT_TAIL rows to its end --
+    // can run in one workgroup (ssor_natural.hip); default 0 (no tail): one CU is slower
+    // (PNP config 3: 2.36 ms per application without, 3.29 / 4.83 ms with 512 / 1024-row tails,
+    // profiles/r04/ssor_natural_tail_r4e.log)
+    static const int tail_rows = [] {
+      const char *ev = std::getenv("PNP_NAT_TAIL");
+      return ev ? std::max(0, std::atoi(ev)) : 0;
+    }();
+    // PNP_NAT_CHAIN (rows): the tail as chains (k_ssor_nat_chain; takes precedence over
+    // PNP_NAT_TAIL).  Default: the levels of at most as many rows as the chain kernel keeps
+    // groups resident (8,192 on MI355X), so that no two chains share a group at one level
+    // (pore_pnp k=4 per application, PB 1.31 -> 0.57 ms, PNP config 3 2.22 -> 1.57 ms;
+    // threshold sweep profiles/r04/chain2/).  PNP_NAT_CHAIN=0: dataflow units only
+    static const int chain_rows = [] {
+      const char *ev = std::getenv("PNP_NAT_CHAIN");
+      return ev ? std::max(0, std::atoi(ev)) : std::max(0, pnp::ssor_natural_chain_capacity());
+    }();
+    const int trows = chain_rows > 0 ? chain_rows : tail_rows;
+    int ltail = nlev;
+    while (trows > 0 && ltail > 0 && lptr[ltail] - lptr[ltail - 1] <= trows) ltail--;
+    W.chain_ok = false;
+    if (chain_rows > 0 && ltail < nlev) {
+      // heavy-path chains of the tail: parent = the first dependency on the level just before
+      // (inside the tail); each row continues the chain of its child with the longest path
+      // below it; chains packed into lane groups by level interval (greedy, by start level)
+      const int t0 = lptr[ltail], t1 = lptr[nlev];
+      auto isdep = [&](int R, int C) {
+        return C != R && !empty(C) && (fwd ? C < R : C > R);
+      };
+      std::vector<int> parent(n, -1), heavy(n, -1), hbest(n, 0);
+      int wmax = 0;
+      for (int t = t0; t < t1; t++) {
+        const int R = rl[t];
+        wmax = std::max(wmax, cnt[R + 1] - cnt[R]);
         for (int k = cnt[R]; k < cnt[R + 1]; k++) {
           const int C = col[k];
-          if (C != R && (fwd ? C < R : C > R) && !empty(C)) l = std::max(l, lev[C] + 1);
-        }
-        lev[R] = l;
-        nlev = std::max(nlev, l + 1);
-        for (int k = cnt[R]; k < cnt[R + 1]; k++) {
-          const int C = col[k];
-          if (C != R && (fwd ? C > R : C < R) && !empty(C)) push[C] = std::max(push[C], l + 1);
-        }
-      }
-      lptr.assign(nlev + 1, 0);
-      for (int R = 0; R < n; R++)
-        if (lev[R] >= 0) lptr[lev[R] + 1]++;
-      for (int l = 0; l < nlev; l++) lptr[l + 1] += lptr[l];
-      std::vector<int> fill(lptr.begin(), lptr.end() - 1), rl(std::max(1, lptr[nlev]));
-      for (int R = 0; R < n; R++)
-        if (lev[R] >= 0) rl[fill[lev[R]]++] = R;
-      // per level an ELL of its rows' entries (CSR order), width = its longest row, padding
-      // slots with value index -1, stored unit by unit: the level's rows in groups of UR (the
-      // dataflow units), each group's entries k-major, entry k of the group's row r at
-      // (group * width + k) * UR + r.  A unit's slots are then one contiguous run of lines that no
-      // other unit touches (column-major over the whole level, 4 units shared every line of a
-      // slot, fetched once per XCD that ran one of them: the PNP head missed L2 ~16.7 M times per
-      // launch, profiles/r05/nat_pmc_mem_r5a.json)
-      const int UR = pnp::ssor_natural_unit_rows();
-      std::vector<int4> info(std::max(1, lptr[nlev]));
-      std::vector<int> lwidth(nlev, 0);
-      W.eoff.assign(nlev + 1, 0);
-      for (int l = 0; l < nlev; l++) {
-        int w = 0;
-        for (int t = lptr[l]; t < lptr[l + 1]; t++) w = std::max(w, cnt[rl[t] + 1] - cnt[rl[t]]);
-        lwidth[l] = w;
-        W.eoff[l + 1] = W.eoff[l] + (long long)w * UR * ((lptr[l + 1] - lptr[l] + UR - 1) / UR);
-      }
-      // operand codes (NatSweep): the forward sweep reads the new value of an earlier row (C < R)
-      // and zero for the row itself and later rows; the backward sweep reads the forward value of
-      // rows C <= R and the new backward value of later rows; rows of other ranks read zero
-      std::vector<int> ecol(std::max<long long>(1, W.eoff[nlev]), -1);
-      for (int l = 0; l < nlev; l++) {
-        for (int t = lptr[l]; t < lptr[l + 1]; t++) {
-          const int R = rl[t], len = cnt[R + 1] - cnt[R], tl = t - lptr[l];
-          info[t] = make_int4(R, len | (diag[R] - cnt[R]) << 8, cnt[R], P(R));
-          for (int k = 0; k < len; k++) {
-            const size_t q =
-                size_t(W.eoff[l]) + (size_t(tl / UR) * lwidth[l] + k) * UR + size_t(tl % UR);
-            const int C = col[cnt[R] + k];
-            ecol[q] = empty(C) ? -1 : fwd ? (C < R ? C : -1) : (C <= R ? C : -(C + 2));
-          }
-        }
-      }
-      // dataflow units for the one-launch sweep: up to ssor_natural_unit_rows() consecutive rows of one level,
-      // {first sweep position, rows | width << 8, the ELL stride between a row's entries (UR), ELL
-      // index of the unit's first row}; forward units in level order, then backward units in level
-      // order.  The
-      // sweep's tail -- the levels from the last one wider than PNP_NAT_TAIL rows to its end --
-      // can run in one workgroup (ssor_natural.hip); default 0 (no tail): one CU is slower
-      // (PNP config 3: 2.36 ms per application without, 3.29 / 4.83 ms with 512 / 1024-row tails,
-      // profiles/r04/ssor_natural_tail_r4e.log)
-      static const int tail_rows = [] {
-        const char *ev = std::getenv("PNP_NAT_TAIL");
-        return ev ? std::max(0, std::atoi(ev)) : 0;
-      }();
-      // PNP_NAT_CHAIN (rows): the tail as chains (k_ssor_nat_chain; takes precedence over
-      // PNP_NAT_TAIL).  Default: the levels of at most as many rows as the chain kernel keeps
-      // groups resident (8,192 on MI355X), so that no two chains share a group at one level
-      // (pore_pnp k=4 per application, PB 1.31 -> 0.57 ms, PNP config 3 2.22 -> 1.57 ms;
-      // threshold sweep profiles/r04/chain2/).  PNP_NAT_CHAIN=0: dataflow units only
-      static const int chain_rows = [] {
-        const char *ev = std::getenv("PNP_NAT_CHAIN");
-        return ev ? std::max(0, std::atoi(ev)) : std::max(0, pnp::ssor_natural_chain_capacity());
-      }();
-      const int trows = chain_rows > 0 ? chain_rows : tail_rows;
-      int ltail = nlev;
-      while (trows > 0 && ltail > 0 && lptr[ltail] - lptr[ltail - 1] <= trows) ltail--;
-      W.chain_ok = false;
-      if (chain_rows > 0 && ltail < nlev) {
-        // heavy-path chains of the tail: parent = the first dependency on the level just before
-        // (inside the tail); each row continues the chain of its child with the longest path
-        // below it; chains packed into lane groups by level interval (greedy, by start level)
-        const int t0 = lptr[ltail], t1 = lptr[nlev];
-        auto isdep = [&](int R, int C) {
-          return C != R && !empty(C) && (fwd ? C < R : C > R);
-        };
-        std::vector<int> parent(n, -1), heavy(n, -1), hbest(n, 0);
-        int wmax = 0;
-        for (int t = t0; t < t1; t++) {
-          const int R = rl[t];
-          wmax = std::max(wmax, cnt[R + 1] - cnt[R]);
-          for (int k = cnt[R]; k < cnt[R + 1]; k++) {
-            const int C = col[k];
-            if (isdep(R, C) && lev[C] == lev[R] - 1 && lev[C] >= ltail) {
-              parent[R] = C;
-              break;
-            }
-          }
-        }
-        for (int t = t1 - 1; t >= t0; t--) {  // decreasing level
-          const int R = rl[t], P = parent[R], h = 1 + hbest[R];
-          if (P >= 0 && h > hbest[P]) {
-            hbest[P] = h;
-            heavy[P] = R;
-          }
-        }
-        // at most the grid's resident lane groups (the kernel's progress needs them all
-        // resident): past that, a chain shares the group that frees first, its rows interleaved
-        // by level (a row whose parent is not the group's previous row reads it from memory)
-        const int gcap = std::max(1, pnp::ssor_natural_chain_capacity());
-        std::vector<std::vector<int>> grows;
-        std::priority_queue<std::pair<int, int>, std::vector<std::pair<int, int>>,
-                            std::greater<std::pair<int, int>>> freeq;  // (end level, group)
-        bool shared = false;
-        long long rr = 0;  // over the cap: chains dealt round-robin (a balanced share per group)
-        std::vector<int> gend;  // each group's last level; heap entries that disagree are stale
-        for (int t = t0; t < t1; t++) {
-          const int R = rl[t];
-          if (parent[R] >= 0 && heavy[parent[R]] == R) continue;  // inside a chain
-          while (!freeq.empty() && freeq.top().first != gend[freeq.top().second]) freeq.pop();
-          int g;
-          if (!freeq.empty() && freeq.top().first < lev[R]) {
-            g = freeq.top().second;
-            freeq.pop();
-          } else if (int(grows.size()) >= gcap) {
-            g = int(rr++ % gcap);
-            shared = true;
-          } else {
-            g = int(grows.size());
-            grows.emplace_back();
-            gend.push_back(-1);
-          }
-          int X = R, last = lev[R];
-          for (; X >= 0; X = heavy[X]) {
-            grows[g].push_back(X);
-            last = lev[X];
-          }
-          gend[g] = std::max(gend[g], last);
-          freeq.push({gend[g], g});
-        }
-        if (shared)  // every group's rows in level order (stable: a chain's rows stay in order)
-          for (auto &G : grows)
-            std::stable_sort(G.begin(), G.end(), [&](int a, int b) { return lev[a] < lev[b]; });
-        const int wpad = wmax;
-        if (wpad <= pnp::ssor_natural_chain_width()) {
-          std::vector<int> gptr(1, 0), ecode;
-          std::vector<int4> rec;
-          for (const auto &G : grows) {
-            const int H = pnp::ssor_natural_chain_history();
-            for (size_t t = 0; t < G.size(); t++) {
-              const int R = G[t];
-              const int len = cnt[R + 1] - cnt[R];
-              rec.push_back(make_int4(R, len | (diag[R] - cnt[R]) << 8, cnt[R], P(R)));
-              for (int k = 0; k < wpad; k++) {
-                if (k < len) {
-                  const int C = col[cnt[R] + k];
-                  const int fc = empty(C) ? -1 : fwd ? (C < R ? C : -1) : (C <= R ? C : -(C + 2));
-                  // kind: 0 zero, 1 forward value, 2 backward value, 3 in the wave's registers
-                  int code = fc == -1 ? 0 : fc >= 0 ? (fc << 2 | 1) : ((-(fc + 2)) << 2 | 2);
-                  const bool fresh = fwd ? (code & 3) == 1 : (code & 3) == 2;  // this sweep's value
-                  for (int h = 1; fresh && h <= H && size_t(h) <= t; h++)
-                    if (G[t - h] == C) {
-                      code = h << 2 | 3;
-                      break;
-                    }
-                  ecode.push_back(code);
-                } else {
-                  ecode.push_back(0);
-                }
-              }
-            }
-            gptr.push_back(int(rec.size()));
-          }
-          int rc2;
-          if ((rc2 = upv(W.cgptr, gptr, "natural SSOR chains")) ||
-              (rc2 = upv(W.crec, rec, "natural SSOR chains")) ||
-              (rc2 = upv(W.cecode, ecode, "natural SSOR chains")))
-            return rc2;
-          W.chain_groups = int(grows.size());
-          W.chain_wpad = wpad;
-          W.chain_ok = true;
-        }
-      }
-      if (chain_rows > 0 && !W.chain_ok) {
-        // no chains (rows wider than the chain kernel takes): the tail is PNP_NAT_TAIL's again
-        // (default none), not the chain threshold's -- a one-workgroup tail of ~8K rows would run
-        // every narrow level on one CU
-        ltail = nlev;
-        while (tail_rows > 0 && ltail > 0 && lptr[ltail] - lptr[ltail - 1] <= tail_rows) ltail--;
-      }
-      for (int l = 0; l < nlev && nat_units_ok; l++) {
-        if (l == ltail) (fwd ? nat_tail_f : nat_tail_b) = int(nat_units.size());
-        const long long w = lwidth[l];
-        for (int t0 = lptr[l]; t0 < lptr[l + 1]; t0 += UR) {
-          const long long e0 = W.eoff[l] + (t0 - lptr[l]) / UR * w * UR;
-          if (w > 255 || W.eoff[l + 1] > INT32_MAX) {
-            nat_units_ok = false;
+          if (isdep(R, C) && lev[C] == lev[R] - 1 && lev[C] >= ltail) {
+            parent[R] = C;
             break;
           }
-          const int rows = std::min(UR, lptr[l + 1] - t0);
-          nat_units.push_back(make_int4(t0, rows | int(w) << 8 | (fwd ? 0 : 1 << 16), UR, int(e0)));
-          nat_max_width = std::max(nat_max_width, int(w));
         }
       }
-      if (ltail >= nlev) (fwd ? nat_tail_f : nat_tail_b) = int(nat_units.size());
-      if (fwd) nat_units_f = int(nat_units.size());
-      int rc2;
-      if ((rc2 = upv(W.info, info, "natural SSOR rows"))) return rc2;
-      return upv(W.ecol, ecol, "natural SSOR columns");
-    };
-    nat_units.clear();
-    nat_units_ok = true;
-    nat_resident = -1;
-    nat_max_width = 0;
-    if ((rc = schedule(true, nat_f)) || (rc = schedule(false, nat_b))) return rc;
-    if (nat_units_ok && (rc = upv(d_nat_units, nat_units, "natural SSOR units"))) return rc;
-    const int ni = std::max(1, nf * (L.n_owned + L.n_ghost));  // internal layout
-    if ((e = nat_d.alloc(std::max(1, n))) != hipSuccess || (e = nat_v.alloc(std::max(1, n))) != hipSuccess ||
-        (e = nat_vf.alloc(std::max(1, n))) != hipSuccess || (e = nat_di.alloc(ni)) != hipSuccess ||
-        (e = nat_vi.alloc(ni)) != hipSuccess || (e = nat_abort.alloc(4)) != hipSuccess ||
-        (e = hipMemset(nat_abort.p, 0, 16)) != hipSuccess)
-      return hipfail(e, "natural SSOR vectors");
-    csr_nnz = nnz;
-    csr_pat = mask;
-    csr_nf = nf;
-    csr_vals_valid = false;
-    return PNP_OK;
-  }
-
-  // the CSR view's values from the current k-form matrix (once per assembly)
-  int csr_values() {
-    int rc;
-    if ((rc = csr_structure())) return rc;
-    if (csr_vals_valid) return nat_probe_run();
-    if ((rc = ensure_values())) return rc;
-    hipError_t e = pnp::launch_csr_fill(dl, nf, pat, vals.p, csr_nnz, csr_src.p, csr_vidx.p,
-                                        csr_val.p, stream);
-    if (e != hipSuccess) return hipfail(e, "csr fill");
-    csr_vals_valid = true;
-    return nat_probe_run();
-  }
-
-  // v = SSOR_natural^{-1} d on internal-layout owned rows (ssor_natural.hip); csr_values() first
-  // (internal layout, owned rows; d == vout allowed: the result is gathered into vout after both
-  // sweeps)
-  hipError_t ssor_natural(const double *d, double *vout) { return nat_sweep(d, vout); }
-  // one launch for both sweeps (ssor_natural.hip, launch_ssor_natural_flow) whenever this context
-  // owns its GPU: one rank, or one rank of an RCCL communicator (one process per GPU, each rank
-  // sweeping its owned rows -- block Jacobi across ranks, as ISTL's NOVLP SeqSSOR on the local
-  // matrix).  The in-process local group keeps the level launches: its ranks share one device, and
-  // the dataflow needs every workgroup of its grid resident.  PNP_NAT_FLOW=0 keeps the level
-  // launches everywhere
-  bool use_nat_flow() const {
-    static const bool env_on = [] {
-      const char *ev = std::getenv("PNP_NAT_FLOW");
-      return !(ev && std::atoi(ev) == 0);
-    }();
-    return nat_resident != 0 &&
-           (nat_flow_opt == 0   ? false
-            : nat_flow_opt == 1 ? nat_units_ok
-                                : env_on && !lg && !host_tr() && nat_units_ok);
-  }
-  int nat_flow_opt = -1;  // PNP_OPT_NAT_FLOW: -1 auto (above), 0 level launches, 1 dataflow
-  // the dataflow's progress needs its whole grid resident: checked once per schedule on the device
-  // (pnp::ssor_natural_flow_resident) before the first dataflow application; 0 keeps the level
-  // launches (the same results bit for bit).  -1 not yet checked
-  int nat_resident = -1;
-  DBuf<unsigned> nat_probe;
-  int nat_probe_run() {
-    if (nat_resident >= 0 || !use_nat_flow()) return PNP_OK;
-    // test hook: PNP_NAT_PROBE_FAIL=1 takes the probe's "not resident" answer without running it
-    // (tests/test_gpu_ssor_natural.py: the level launches are then used, bitwise the same)
-    if (const char *ev = std::getenv("PNP_NAT_PROBE_FAIL"); ev && std::atoi(ev) == 1) {
-      nat_resident = 0;
-      return PNP_OK;
-    }
-    hipError_t e = nat_probe.p ? hipSuccess : nat_probe.alloc(2);
-    if (e != hipSuccess) return hipfail(e, "natural SSOR probe");
-    const int r = pnp::ssor_natural_flow_resident(nat_flow_view(), nat_probe.p, stream);
-    if (r < 0) return fail(PNP_E_HIP, "natural SSOR: co-residency probe failed");
-    nat_resident = r;
-    return PNP_OK;
-  }
-  long long nat_flow_n = 0, nat_level_n = 0;  // applications per schedule (pnp_info)
-  hipError_t nat_sweep(const double *d, double *vout) {
-    if (use_nat_flow()) {
-      nat_flow_n++;
-      return ssor_natural_flow(d, vout);
-    }
-    nat_level_n++;
-    return ssor_natural_levels(d, vout);
-  }
-  pnp::NatFlow nat_flow_view() const {
-    pnp::NatFlow F;
-    F.units = d_nat_units.p;
-    F.nunits = int(nat_units.size());
-    F.nunits_f = nat_units_f;
-    F.tail_f = nat_tail_f;
-    F.tail_b = nat_tail_b;
-    F.max_width = nat_max_width;
-    F.chain_f = nat_f.chains();
-    F.chain_b = nat_b.chains();
-    F.fwd = nat_f.view();
-    F.bwd = nat_b.view();
-    F.abort_word = nat_abort.p;
-    return F;
-  }
-  hipError_t ssor_natural_flow(const double *d, double *vout) {
-    const pnp::NatFlow F = nat_flow_view();
-    hipError_t e = pnp::launch_ssor_natural_flow(F, nf * mesh.nv, csr_val.p, d, nat_vf.p, nat_v.p,
-                                                 stream);
-    // the result out of the external-layout vb (storing it at internal positions from the
-    // backward kernels as well cost more than this gather: +40 against 22 us, r5f)
-    if (e == hipSuccess)
-      e = pnp::launch_gather_ext(L.n_owned, nf, mesh.nv, d_l2g.p, nat_v.p, vout, stream);
-    return e;
-  }
-  // a dataflow sweep that timed out (never expected: every unit waits only on earlier units, all
-  // resident) leaves NaN results and a sticky word; the solve reports it as an error
-  int nat_check() {
-    if (!use_nat_flow() || !nat_abort.p) return PNP_OK;
-    unsigned w = 0;
-    hipError_t e = hipMemcpyAsync(&w, nat_abort.p, 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "natural SSOR status");
-    if (w) {
-      hipMemsetAsync(nat_abort.p, 0, 16, stream);
-      return fail(PNP_E_HIP, "natural SSOR: dataflow sweep timed out waiting for an operand");
-    }
-    return PNP_OK;
-  }
-  // ---- ILU(0) application as one dataflow launch (PNP_OPT_ILU_FLOW) -----------------------------
-  // Units in the colour launches' order (forward colours c_first .. nc-2, the last colour, backward
-  // colours nc-2 .. 0), one per 256-position block of the colour.  A unit's dependencies (all
-  // earlier in the order): forward / last -- the forward units of the rows in its L staging list;
-  // backward -- the backward (or last-colour) units of the rows in its U list, the forward units of
-  // its own rows (their forward values are its input) and every forward unit whose L list holds one
-  // of its rows (which must have read that row's forward value before it is overwritten).
-  int ilu_flow_build(int c_first, IluFlowDev &D) {
-    D.built = true;
-    D.ok = false;
-    const int nc = int(L.color_ptr.size()) - 1;
-    const std::vector<int> &cp = L.color_ptr;
-    if (!dl.lsx_ptr || nc < 2 || h_posrowL.empty()) return PNP_OK;
-    std::vector<int> nb(nc), blk0(nc + 1, 0);
-    for (int c = 0; c < nc; c++) {
-      nb[c] = (cp[c + 1] - cp[c] + 255) / 256;
-      blk0[c + 1] = blk0[c] + nb[c];
-    }
-    std::vector<std::pair<int, int>> stages;  // {kind, colour}
-    for (int c = c_first; c < nc - 1; c++) stages.push_back({0, c});
-    stages.push_back({2, nc - 1});
-    for (int c = nc - 2; c >= 0; c--) stages.push_back({1, c});
-    if (int(stages.size()) > pnp::kIluFlowMaxStages) return PNP_OK;
-    pnp::IluFlow F;
-    F.nstages = int(stages.size());
-    int nu = 0;
-    for (int s = 0; s < F.nstages; s++) {
-      const int c = stages[s].second;
-      F.unit0[s] = nu;
-      F.kind[s] = stages[s].first;
-      F.r0[s] = cp[c];
-      F.r1[s] = cp[c + 1];
-      F.blk0[s] = blk0[c];
-      nu += nb[c];
-    }
-    F.unit0[F.nstages] = nu;
-    F.nunits = nu;
-    const int no = L.n_owned;
-    std::vector<int> fwdu(no, -1), bwdu(no, -1);
-    for (int s = 0; s < F.nstages; s++) {
-      const int c = stages[s].second, kind = stages[s].first;
-      for (int p = cp[c]; p < cp[c + 1]; p++) {
-        const int u = F.unit0[s] + (p - cp[c]) / 256;
-        if (kind != 1) fwdu[h_posrowL[p]] = u;
-        if (kind != 0) bwdu[h_posrowU[p]] = u;
-      }
-    }
-    // readers[r]: forward / last units whose L list holds row r (CSR)
-    std::vector<int> rptr(no + 1, 0), rdr;
-    auto lblock = [&](int s, int u) { return F.blk0[s] + (u - F.unit0[s]); };
-    for (int pass = 0; pass < 2; pass++) {
-      for (int s = 0; s < F.nstages; s++) {
-        if (F.kind[s] == 1) continue;
-        for (int u = F.unit0[s]; u < F.unit0[s + 1]; u++) {
-          const int b = lblock(s, u);
-          for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++) {
-            const int j = h_lsx_list[k];
-            if (pass == 0)
-              rptr[j + 1]++;
-            else
-              rdr[rptr[j]++] = u;
-          }
+      for (int t = t1 - 1; t >= t0; t--) {  // decreasing level
+        const int R = rl[t], P = parent[R], h = 1 + hbest[R];
+        if (P >= 0 && h > hbest[P]) {
+          hbest[P] = h;
+          heavy[P] = R;
         }
       }
-      if (pass == 0) {
-        for (int r = 0; r < no; r++) rptr[r + 1] += rptr[r];
-        rdr.assign(rptr[no], 0);
-      } else {
-        for (int r = no; r > 0; r--) rptr[r] = rptr[r - 1];
-        rptr[0] = 0;
-      }
-    }
-    std::vector<int> dptr(nu + 1, 0), dlist, dep;
-    for (int s = 0; s < F.nstages; s++) {
-      const int c = stages[s].second;
-      for (int u = F.unit0[s]; u < F.unit0[s + 1]; u++) {
-        const int b = lblock(s, u);
-        dep.clear();
-        if (F.kind[s] != 1) {
-          for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++)
-            if (fwdu[h_lsx_list[k]] >= 0) dep.push_back(fwdu[h_lsx_list[k]]);
+      // at most the grid's resident lane groups (the kernel's progress needs them all
+      // resident): past that, a chain shares the group that frees first, its rows interleaved
+      // by level (a row whose parent is not the group's previous row reads it from memory)
+      const int gcap = std::max(1, pnp::ssor_natural_chain_capacity());
+      std::vector<std::vector<int>> grows;
+      std::priority_queue<std::pair<int, int>, std::vector<std::pair<int, int>>,
+                          std::greater<std::pair<int, int>>> freeq;  // (end level, group)
+      bool shared = false;
+      long long rr = 0;  // over the cap: chains dealt round-robin (a balanced share per group)
+      std::vector<int> gend;  // each group's last level; heap entries that disagree are stale
+      for (int t = t0; t < t1; t++) {
+        const int R = rl[t];
+        if (parent[R] >= 0 && heavy[parent[R]] == R) continue;  // inside a chain
+        while (!freeq.empty() && freeq.top().first != gend[freeq.top().second]) freeq.pop();
+        int g;
+        if (!freeq.empty() && freeq.top().first < lev[R]) {
+          g = freeq.top().second;
+          freeq.pop();
+        } else if (int(grows.size()) >= gcap) {
+          g = int(rr++ % gcap);
+          shared = true;
         } else {
-          for (int k = h_usx_ptr[b]; k < h_usx_ptr[b + 1]; k++)
-            if (bwdu[h_usx_list[k]] >= 0) dep.push_back(bwdu[h_usx_list[k]]);
-          const int p0 = cp[c] + 256 * (u - F.unit0[s]), p1 = std::min(cp[c + 1], p0 + 256);
-          for (int p = p0; p < p1; p++) {
-            const int r = h_posrowU[p];
-            if (fwdu[r] >= 0) dep.push_back(fwdu[r]);
-            for (int k = rptr[r]; k < rptr[r + 1]; k++) dep.push_back(rdr[k]);
-          }
+          g = int(grows.size());
+          grows.emplace_back();
+          gend.push_back(-1);
         }
-        std::sort(dep.begin(), dep.end());
-        dep.erase(std::unique(dep.begin(), dep.end()), dep.end());
-        for (int w : dep)
-          if (w >= u) return fail(PNP_E_STATE, "ILU(0) dataflow: a unit depends on a later one");
-        dlist.insert(dlist.end(), dep.begin(), dep.end());
-        dptr[u + 1] = int(dlist.size());
-      }
-    }
-    if (dlist.empty()) dlist.push_back(0);
-    auto upv = [&](auto &buf, const auto &vec, const char *what) -> int {
-      hipError_t e2 = buf.alloc(vec.size());
-      if (e2 == hipSuccess)
-        e2 = hipMemcpy(buf.p, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice);
-      return e2 == hipSuccess ? PNP_OK : hipfail(e2, what);
-    };
-    int rc;
-    if ((rc = upv(D.dep_ptr, dptr, "ILU(0) dataflow deps")) ||
-        (rc = upv(D.dep_list, dlist, "ILU(0) dataflow deps")))
-      return rc;
-    hipError_t e = D.flags.alloc(size_t(nu + 1 + 3) & ~size_t(3));
-    if (e == hipSuccess && !ilu_flow_abort.p) {
-      e = ilu_flow_abort.alloc(4);
-      if (e == hipSuccess) e = hipMemset(ilu_flow_abort.p, 0, 16);
-    }
-    if (e != hipSuccess) return hipfail(e, "ILU(0) dataflow flags");
-    F.dep_ptr = D.dep_ptr.p;
-    F.dep_list = D.dep_list.p;
-    F.flags = D.flags.p;
-    F.abort_word = ilu_flow_abort.p;
-    D.F = F;
-    D.ok = true;
-    return PNP_OK;
-  }
-  // v = ILU(0)^-1 d over the owned rows, colours from c_first (launch_ilu0_apply's contract): one
-  // dataflow launch when PNP_OPT_ILU_FLOW is on and d and v are distinct, else the colour launches
-  int ilu_apply(const double *d, double *vout, int c_first, const char *what,
-                hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
-    // the resident-grid form needs the device to itself: not with in-process ranks sharing it
-    // (and one context per GPU at N > 1); PNP_ILU_FLOW_TICKET=1: the ticketed form (any residency)
-    // PNP_ILU_FLOW_MODE: IluFlow::persistent (0 ticket, 1 static resident grid, the default).
-    // A third form, a resident grid over 8 ticketed queues, hung in the bitwise tests (killed
-    // after 180 s of silence, gpurun_out r4i) and was removed
-    static const int mode = [] {
-      const char *ev = std::getenv("PNP_ILU_FLOW_MODE");
-      const int m = ev ? std::atoi(ev) : 1;
-      return (m >= 0 && m <= 1) ? m : 1;
-    }();
-    // PNP_OPT_ILU_FLOW = 2 selects the ticketed form (any residency, so also ranks sharing a GPU)
-    const int fmode = ilu_flow_opt == 2 ? 0 : mode;
-    if (ilu_flow_opt && d != vout && (c_first == 0 || c_first == 1) && (fmode == 0 || !dist)) {
-      IluFlowDev &D = ilu_flow[c_first];
-      int rc;
-      if (!D.built && (rc = ilu_flow_build(c_first, D))) return rc;
-      D.F.persistent = fmode;
-      if (D.ok) {
-        if (t0) hipEventRecord(t0, stream);
-        hipError_t e = pnp::launch_ilu0_flow(dl, D.F, nf, pat, lvals.p, uvals.p, d, vout, stream,
-                                             f32_now());
-        if (t1) hipEventRecord(t1, stream);
-        if (e != hipSuccess) return hipfail(e, what);
-        ilu_flow_used = true;
-        ilu_flow_n++;
-        return PNP_OK;
-      }
-    }
-    hipError_t e = pnp::launch_ilu0_apply(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, d,
-                                          vout, stream, c_first, nullptr, nullptr, f32_now(),
-                                          ilu_y32(), t0, t1);
-    return e == hipSuccess ? PNP_OK : hipfail(e, what);
-  }
-  // a dataflow application that timed out (never expected) leaves void results and a sticky word
-  int ilu_flow_check() {
-    if (!ilu_flow_used || !ilu_flow_abort.p) return PNP_OK;
-    ilu_flow_used = false;
-    unsigned w = 0;
-    hipError_t e = hipMemcpyAsync(&w, ilu_flow_abort.p, 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "ILU(0) dataflow status");
-    if (w) {
-      hipMemsetAsync(ilu_flow_abort.p, 0, 16, stream);
-      return fail(PNP_E_HIP, "ILU(0) dataflow application timed out waiting for a unit");
-    }
-    return PNP_OK;
-  }
-  // the level launches: one graph replay (captured on first use; PNP_NAT_GRAPH=0: eager), or eager
-  // when the stream is itself being captured (a BiCGSTAB block graph then holds them), with more
-  // than one rank, or after a failed capture
-  // (on the context's external-layout nat_d / nat_v, so that the captured level graph's arguments
-  // stay valid whatever vectors the caller passes)
-  hipError_t ssor_natural_levels(const double *d, double *vout) {
-    const int nv = mesh.nv;
-    hipError_t e = pnp::launch_scatter_ext(L.n_owned, nf, nv, d_l2g.p, d, nat_d.p, stream);
-    if (e == hipSuccess) e = ssor_natural_levels_fixed();
-    if (e == hipSuccess) e = pnp::launch_gather_ext(L.n_owned, nf, nv, d_l2g.p, nat_v.p, vout, stream);
-    return e;
-  }
-  hipError_t ssor_natural_levels_fixed() {
-    auto issue = [&] {
-      hipError_t e0 = hipMemsetAsync(nat_v.p, 0, sizeof(double) * nat_v.n, stream);
-      return e0 != hipSuccess ? e0
-                              : pnp::launch_ssor_natural(nat_f.view(), nat_b.view(), csr_val.p,
-                                                         nat_d.p, nat_v.p, stream);
-    };
-    static const bool env_on = [] {
-      const char *ev = std::getenv("PNP_NAT_GRAPH");
-      return !(ev && std::atoi(ev) == 0);
-    }();
-    // not with more than one rank: in-process ranks share the device, and another rank's thread
-    // touching the legacy stream during a capture would invalidate it
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (!env_on || dist || nat_graph_failed || profiled() ||
-        hipStreamIsCapturing(stream, &cs) != hipSuccess ||
-        cs != hipStreamCaptureStatusNone)
-      return issue();
-    if (!nat_exec) {
-      hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
-      if (e == hipSuccess) {
-        const hipError_t e1 = issue();
-        hipGraph_t g = nullptr;
-        const hipError_t e2 = hipStreamEndCapture(stream, &g);
-        e = e1 != hipSuccess ? e1 : e2;
-        if (e == hipSuccess) e = hipGraphInstantiate(&nat_exec, g, nullptr, nullptr, 0);
-        if (g) hipGraphDestroy(g);
-      }
-      if (e != hipSuccess || !nat_exec) {  // nothing of the capture ran: launch eagerly
-        (void)hipGetLastError();
-        nat_exec = nullptr;
-        nat_graph_failed = true;
-        return issue();
-      }
-    }
-    return hipGraphLaunch(nat_exec, stream);
-  }
-
-  // analytic (k-form) or forward-difference (expanded, kPat*FD) storage of the next Jacobian
-  int set_fd(bool on) {
-    if (on == fd_mode) return PNP_OK;
-    graphs_clear();
-    int rc;
-    // P_k: the element kernel differentiates by itself; scalar blocks need no FD value layout
-    if (on && !fd_built && degree == 1 && (rc = fd_build())) return rc;
-    const int base = kind == PNP_OP_PNP ? pnp::kPatPnp
-                                        : (kind == PNP_OP_PNP_IMPLICIT_EULER ? pnp::kPatPnpIE
-                                                                            : pnp::kPatScalar);
-    pat = (on && nf == 3) ? (base | pnp::kPatFD) : base;
-    nks = pnp::nks_of(pat);
-    fd_mode = on;
-    assembled = false;
-    lu_valid = false;
-    split_of = 0;
-    amg_valid = false;
-    vals_const_valid = false;  // another value layout, zeroed below
-    if (on && degree == 1) {
-      // one-step operators keep two matrices per element (spatial, temporal: fd_jacobian.hip)
-      const size_t need = size_t(fd_ne) * 9 * nf * nf * 2;
-      if (fd_jel.n < need) {
-        hipError_t e = fd_jel.alloc(need);
-        if (e != hipSuccess) return hipfail(e, "fd element matrices");
-      }
-    }
-    // padding slots must read as zeros in the new value layout (the SpMV multiplies them)
-    hipError_t e = hipMemsetAsync(vals.p, 0, sizeof(double) * size_t(L.nslots) * nks, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "clear matrix");
-  }
-
-  // P_k element lists (once per context): the local elements (every element with an owned node,
-  // ascending global id) and their local nodes (SoA); per owned row its incident elements in
-  // ascending order, in SELL-chunk layout (PkDev), with the row's slot of every element node
-  int pk_build() {
-    const pnp::Mesh &m = tmesh;
-    const int nl = pks.nl, nw = (nl + 3) / 4;
-    std::vector<int> en;
-    std::vector<int> elist;
-    for (int e = 0; e < m.nt; e++) {
-      const int *g = &pks.enode[size_t(e) * nl];
-      bool mine = false, local = true;
-      for (int a = 0; a < nl; a++) {
-        const int l = L.g2l[g[a]];
-        mine = mine || (l >= 0 && l < L.n_owned);
-        local = local && l >= 0;
-      }
-      if (!mine) continue;
-      if (!local) return fail(PNP_E_MESH, "P_k: element not local");
-      elist.push_back(e);
-    }
-    const int ne = int(elist.size());
-    if (ne >= (1 << 27)) return fail(PNP_E_MESH, "P_k: too many local elements");
-    en.resize(size_t(ne) * nl);
-    for (int e = 0; e < ne; e++)
-      for (int a = 0; a < nl; a++) en[size_t(a) * ne + e] = L.g2l[pks.enode[size_t(elist[e]) * nl + a]];
-    auto slot_of = [&](int row, int col) -> int {
-      const int ch = row / pnp::kRows, ln = row % pnp::kRows, len = pnp::meta_len(L.rowmeta[row]);
-      if (col == row) return 0;
-      for (int sl = 1; sl < len; sl++)
-        if (L.colidx[L.chunk_off[ch] + 64LL * sl + ln] == col) return sl;
-      return -1;
-    };
-    // incidences per owned row, ascending element order
-    std::vector<int> icnt(L.n_owned, 0);
-    for (int e = 0; e < ne; e++)
-      for (int a = 0; a < nl; a++) {
-        const int ra = en[size_t(a) * ne + e];
-        if (ra < L.n_owned) icnt[ra]++;
-      }
-    std::vector<int> ioff(L.nchunks + 1, 0);
-    for (int c = 0; c < L.nchunks; c++) {
-      int mx = 0;
-      for (int ln = 0; ln < pnp::kRows && c * pnp::kRows + ln < L.n_owned; ln++)
-        mx = std::max(mx, icnt[c * pnp::kRows + ln]);
-      ioff[c + 1] = ioff[c] + pnp::kRows * mx;
-    }
-    std::vector<int> inc(std::max(1, ioff[L.nchunks]), 0), fill(L.n_owned, 0);
-    std::vector<uint32_t> islot(size_t(std::max(1, ioff[L.nchunks])) * nw, 0);
-    for (int e = 0; e < ne; e++)
-      for (int a = 0; a < nl; a++) {
-        const int ra = en[size_t(a) * ne + e];
-        if (ra >= L.n_owned) continue;
-        const int c = ra / pnp::kRows, ln = ra % pnp::kRows;
-        const size_t p = size_t(ioff[c]) + size_t(pnp::kRows) * fill[ra]++ + ln;
-        inc[p] = e << 4 | a;
-        for (int b = 0; b < nl; b++) {
-          const int sl = slot_of(ra, en[size_t(b) * ne + e]);
-          if (sl < 0) return fail(PNP_E_MESH, "P_k: element pair outside the pattern");
-          islot[p * nw + (b >> 2)] |= uint32_t(sl) << (8 * (b & 3));
+        int X = R, last = lev[R];
+        for (; X >= 0; X = heavy[X]) {
+          grows[g].push_back(X);
+          last = lev[X];
         }
+        gend[g] = std::max(gend[g], last);
+        freeq.push({gend[g], g});
       }
-    int rc;
-    if ((rc = upv(pk_enode, en, "P_k elements")) || (rc = upv(pk_ioff, ioff, "P_k ioff")) ||
-        (rc = upv(pk_icnt, icnt, "P_k icnt")) || (rc = upv(pk_inc, inc, "P_k incidences")) ||
-        (rc = upv(pk_islot, islot, "P_k slots")))
-      return rc;
-    hipError_t e = pk_eres.alloc(std::max<size_t>(1, size_t(ne) * nl));
-    if (e != hipSuccess) return hipfail(e, "P_k element residual scratch");
-    e = pk_ejac.alloc(std::max<size_t>(1, size_t(ne) * nl * ((nl + 2) & ~1)));
-    if (e != hipSuccess) return hipfail(e, "P_k element matrix scratch");
-    e = pnp::pk_upload_tables(pks.k, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "P_k tables");
-    pkd.k = pks.k;
-    pkd.nl = nl;
-    pkd.ne = ne;
-    pkd.enode = pk_enode.p;
-    pkd.ioff = pk_ioff.p;
-    pkd.icnt = pk_icnt.p;
-    pkd.inc = pk_inc.p;
-    pkd.islot = pk_islot.p;
-    pkd.eres = pk_eres.p;
-    pkd.ejac = pk_ejac.p;
-    // the Jacobian gather pass accumulates a row's slots in LDS, sized for the longest row: the
-    // vertex rows (up to 55 slots at P3) would hold every workgroup to one per CU.  When the
-    // longest row needs more than 64 KB per workgroup, blocks whose rows are all at most the
-    // median block length (the edge and interior node rows) run in a launch of their own with an
-    // LDS accumulator of that length: P3 438 -> 395 us; at P2 (one launch at 3 workgroups per CU)
-    // the second launch costs more than it gains, 135 -> 145 us (profiles/r02/ab_pk_split).
-    // PNP_PK_SPLIT=0: always one launch, 1: split whenever the median is at most half the longest
-    {
-      const char *ev = getenv("PNP_PK_SPLIT");
-      const int nblk = (L.n_owned + 255) / 256;
-      std::vector<int> order(nblk), blen(nblk, 0);
-      for (int b = 0; b < nblk; b++) order[b] = b;
-      if (dl.blkmap && nblk > 0) {
-        e = hipMemcpy(order.data(), dl.blkmap, sizeof(int) * nblk, hipMemcpyDeviceToHost);
-        if (e != hipSuccess) return hipfail(e, "blkmap");
-      }
-      for (int r = 0; r < L.n_owned; r++)
-        blen[r / 256] = std::max(blen[r / 256], pnp::meta_len(L.rowmeta[r]));
-      std::vector<int> srt(blen);
-      std::nth_element(srt.begin(), srt.begin() + nblk / 2, srt.end());
-      const int T = nblk > 0 ? srt[nblk / 2] : 0;
-      const int mx = nblk > 0 ? *std::max_element(blen.begin(), blen.end()) : 0;
-      const bool want = ev ? ev[0] == '1' : size_t(mx) * 256 * sizeof(double) > 64 * 1024;
-      if (want && nblk > 0 && 2 * T <= mx) {
-        std::vector<int> sh, lo;
-        for (int b : order) (blen[b] <= T ? sh : lo).push_back(b);
-        if ((rc = upv(pk_blk_short, sh, "P_k short blocks")) ||
-            (rc = upv(pk_blk_long, lo, "P_k long blocks")))
-          return rc;
-        pkd.blk_short = pk_blk_short.p;
-        pkd.blk_long = pk_blk_long.p;
-        pkd.n_short = int(sh.size());
-        pkd.n_long = int(lo.size());
-        pkd.short_len = T;
-      }
-    }
-    // ion-flux segments handled by this rank: those whose element is local and whose lower
-    // global vertex is owned here, {local element, face, group}, in global segment order
-    std::vector<int> eloc(m.nt, -1);
-    for (int e2 = 0; e2 < ne; e2++) eloc[elist[e2]] = e2;
-    std::vector<int4> segs;
-    fseg_group.clear();
-    for (int sg = 0; sg < m.nb; sg++) {
-      const int a = m.bseg[2 * size_t(sg)], b = m.bseg[2 * size_t(sg) + 1];
-      const int lo = L.g2l[std::min(a, b)];
-      if (lo < 0 || lo >= L.n_owned) continue;
-      const int bf = pks.bface[sg];
-      if (bf < 0 || eloc[bf / 3] < 0) return fail(PNP_E_MESH, "ion flux: the element of a boundary segment is not local");
-      segs.push_back(make_int4(eloc[bf / 3], bf % 3, m.bgroup[sg], 0));
-      fseg_group.push_back(m.bgroup[sg]);
-    }
-    if ((rc = upv(d_fseg, segs, "P_k flux segments"))) return rc;
-    e = fluxout.alloc(2 * segs.size() + 2);
-    if (e != hipSuccess) return hipfail(e, "flux out");
-    return PNP_OK;
-  }
-
-  // local elements (ascending global id, vertices in mesh order) and, per owned row and slot, the
-  // element entries summed into that block, in ascending element order
-  int fd_build() {
-    const pnp::Mesh &m = mesh;
-    std::vector<int> et;
-    for (int e = 0; e < m.nt; e++) {
-      const int *t = &m.tri[3 * size_t(e)];
-      const int l0 = L.g2l[t[0]], l1 = L.g2l[t[1]], l2 = L.g2l[t[2]];
-      const bool mine = (l0 >= 0 && l0 < L.n_owned) || (l1 >= 0 && l1 < L.n_owned) ||
-                        (l2 >= 0 && l2 < L.n_owned);
-      if (!mine) continue;
-      if (l0 < 0 || l1 < 0 || l2 < 0) return fail(PNP_E_MESH, "FD Jacobian: element not local");
-      et.push_back(l0);
-      et.push_back(l1);
-      et.push_back(l2);
-    }
-    const int ne = int(et.size() / 3);
-    auto pos_of = [&](int row, int col) -> long long {
-      const int ch = row / pnp::kRows, ln = row % pnp::kRows, len = pnp::meta_len(L.rowmeta[row]);
-      if (col == row) return L.chunk_off[ch] + ln;
-      for (int sl = 1; sl < len; sl++) {
-        const long long p = L.chunk_off[ch] + 64LL * sl + ln;
-        if (L.colidx[p] == col) return p;
-      }
-      return -1;
-    };
-    std::vector<int> cnt(size_t(L.nslots) + 1, 0);
-    for (int e = 0; e < ne; e++)
-      for (int a = 0; a < 3; a++) {
-        const int va = et[3 * size_t(e) + a];
-        if (va >= L.n_owned) continue;
-        for (int b = 0; b < 3; b++) {
-          const long long p = pos_of(va, et[3 * size_t(e) + b]);
-          if (p < 0) return fail(PNP_E_MESH, "FD Jacobian: element pair outside the pattern");
-          cnt[p]++;
-        }
-      }
-    // per row: for each slot, the count then its codes
-    std::vector<long long> rptr(L.n_owned + 1, 0);
-    for (int i = 0; i < L.n_owned; i++) {
-      const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
-      long long n = 0;
-      for (int sl = 0; sl < len; sl++) n += 1 + cnt[L.chunk_off[ch] + 64LL * sl + ln];
-      rptr[i + 1] = rptr[i] + n;
-    }
-    std::vector<long long> at((size_t)L.nslots, -1LL);  // next free code position of each block
-    std::vector<int> data((size_t)rptr[L.n_owned]);
-    for (int i = 0; i < L.n_owned; i++) {
-      const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
-      long long q = rptr[i];
-      for (int sl = 0; sl < len; sl++) {
-        const long long p = L.chunk_off[ch] + 64LL * sl + ln;
-        data[q] = cnt[p];
-        at[p] = q + 1;
-        q += 1 + cnt[p];
-      }
-    }
-    for (int e = 0; e < ne; e++)
-      for (int a = 0; a < 3; a++) {
-        const int va = et[3 * size_t(e) + a];
-        if (va >= L.n_owned) continue;
-        for (int b = 0; b < 3; b++) {
-          const long long p = pos_of(va, et[3 * size_t(e) + b]);
-          data[at[p]++] = e * 9 + a * 3 + b;
-        }
-      }
-    int rc;
-    if ((rc = upv(fd_etri, et, "fd elements")) || (rc = upv(fd_rptr, rptr, "fd rptr")) ||
-        (rc = upv(fd_cdata, data, "fd contributions")))
-      return rc;
-    fd_ne = ne;
-    fd_built = true;
-    return PNP_OK;
-  }
-
-  // ILU(0) factors of the current matrix (once per assembly).  Default: the fused factorisation
-  // (expand and split folded in, neighbour-row work hoisted; PNP_OPT_ILU_FUSED_FACTOR = 0 runs the
-  // three-pass path, the same bits)
-  int ilu_factor() {
-    if (lu_valid) return PNP_OK;
-    if (int rc = ensure_values()) return rc;
-    hipEvent_t t0 = tb(T_FACT);
-    hipError_t e;
-    if (ilu_fused) {
-      e = pnp::launch_ilu0_factor_fused(dl, L.color_ptr.data(), nf, pat, vals.p, d_rowoff.p,
-                                        d_rowcol.p, lu.p, lvals.p, uvals.p, ilu_fac(), stream);
-    } else {
-      e = pnp::launch_expand(dl, nf, pat, vals.p, lu.p, stream);
-      if (e == hipSuccess)
-        e = pnp::launch_ilu0_factor(dl, L.color_ptr.data(), nf, pat, lu.p, stream);
-    }
-    if (e != hipSuccess) return hipfail(e, "ilu0 factorisation");
-    te(T_FACT, t0);
-    lu_valid = true;
-    split_of = ilu_fused ? 2 : 0;
-    return PNP_OK;
-  }
-
-  // bring the split storage up to date with the matrix (which = 1) or the factors (which = 2)
-  int split(int which) {
-    if (split_of == which) return PNP_OK;
-    if (which == 2 && ilu_fused) {  // the fused factorisation keeps no SELL copy: redo it
-      lu_valid = false;
-      return ilu_factor();
-    }
-    if (which == 1)
-      if (int rc = ensure_values()) return rc;
-    hipEvent_t t0 = tb(T_FACT);
-    hipError_t e = pnp::launch_split(dl, nf, pat, which == 1 ? 1 : 0, which == 2 ? lu.p : vals.p,
-                                     d_lsrc.p, (long long)d_lsrc.n, d_usrc.p, (long long)d_usrc.n,
-                                     lvals.p, uvals.p, stream, which == 2 ? ilu_fac() : 0);
-    if (e != hipSuccess) return hipfail(e, "split");
-    te(T_FACT, t0);
-    split_of = which;
-    return PNP_OK;
-  }
-
-  // ---- aggregation AMG ------------------------------------------------------------------------
-  template <typename T>
-  int upv(DBuf<T> &d, const std::vector<T> &h, const char *what) {
-    hipError_t e = d.alloc(std::max<size_t>(1, h.size()));
-    if (e == hipSuccess && !h.empty())
-      e = hipMemcpy(d.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
-    return e == hipSuccess ? PNP_OK : hipfail(e, what);
-  }
-
-  // hierarchy patterns (once), value/vector buffers (per field count), coarse values (per
-  // assembly): Galerkin sums, block-diagonal inverses, the coarsest dense inverse
-  int amg_setup() {
-    int rc;
-    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
-    // the Galerkin products and the V-cycle's level-0 residuals read the SELL values
-    if ((rc = ensure_values())) return rc;
-    if (!amg_built) {
-      amg_d.clear();
-      if (!pnp::amg_build(L, amg_opts.coarse_target, amg_opts.max_levels, amg_h, err))
-        return PNP_E_STATE;
-      for (const auto &H : amg_h) {
-        auto D = std::make_unique<AmgDev>();
-        D->nb = H.nb;
-        if ((rc = upv(D->rp, H.rp, "amg rp")) || (rc = upv(D->col, H.col, "amg col")) ||
-            (rc = upv(D->dpos, H.dpos, "amg dpos")) || (rc = upv(D->mptr, H.mptr, "amg mptr")) ||
-            (rc = upv(D->mem, H.mem, "amg mem")) || (rc = upv(D->agg, H.agg, "amg agg")) ||
-            (rc = upv(D->csrc, H.csrc, "amg csrc")) || (rc = upv(D->cptr, H.cptr, "amg cptr")))
-          return rc;
-        amg_d.push_back(std::move(D));
-      }
-      amg_built = true;
-      amg_nf = 0;
-    }
-    if (amg_d.empty()) return fail(PNP_E_STATE, "AMG: no owned rows");
-    const int K = int(amg_d.size());
-    if (amg_d[K - 1]->nb * nf > pnp::kAmgMaxDense)
-      return fail(PNP_E_STATE, "AMG: coarsest level too large for the dense solve");
-    if (amg_nf != nf) {
-      const size_t nb2 = size_t(nf) * nf;
-      for (auto &D : amg_d) {
-        hipError_t e;
-        if ((amg_f32() && D.get() != amg_d.back().get() &&
-             (e = D->vf.alloc(std::max<size_t>(1, D->col.n) * nb2)) != hipSuccess) ||
-            (e = D->v.alloc(std::max<size_t>(1, D->col.n) * nb2)) != hipSuccess ||
-            (e = D->dinv.alloc(size_t(D->nb) * nb2)) != hipSuccess ||
-            (e = D->b.alloc(size_t(D->nb) * nf)) != hipSuccess ||
-            (e = D->x.alloc(size_t(D->nb) * nf)) != hipSuccess ||
-            (e = D->x2.alloc(size_t(D->nb) * nf)) != hipSuccess)
-          return hipfail(e, "amg level buffers");
-      }
-      const size_t nc = size_t(amg_d[K - 1]->nb) * nf, nl = size_t(L.n_owned + L.n_ghost) * nf;
-      hipError_t e;
-      amg_ld = int((nc + 3) & ~size_t(3));
-      if ((amg_f32() && (e = amg_ainv_f.alloc(nc * size_t(amg_ld))) != hipSuccess) ||
-          (e = amg_ainv.alloc(nc * nc)) != hipSuccess || (e = amg_ipiv.alloc(nc)) != hipSuccess ||
-          (e = amg_info.alloc(1)) != hipSuccess ||
-          (e = amg_x0.alloc(nl)) != hipSuccess || (e = amg_t.alloc(nl)) != hipSuccess ||
-          (e = amg_y.alloc(nl)) != hipSuccess || (e = amg_r.alloc(nl)) != hipSuccess ||
-          (e = amg_z.alloc(nl)) != hipSuccess)
-        return hipfail(e, "amg vectors");
-      amg_nf = nf;
-      amg_valid = false;
-    }
-    const int sm = amg_opts.smoother;
-    if (sm == PNP_PREC_SSOR && (rc = split(1))) return rc;
-    if (sm == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
-    if (sm == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
-    if (amg_valid) return PNP_OK;
-    hipEvent_t t0 = tb(T_FACT);
-    double ts = now_s();
-    hipError_t e = pnp::launch_amg_galerkin0(dl, nf, pat, vals.p, (long long)amg_h[0].col.size(),
-                                             amg_d[0]->cptr.p, amg_d[0]->csrc.p, amg_d[0]->v.p,
-                                             stream);
-    for (int k = 1; k < K && e == hipSuccess; k++)
-      e = pnp::launch_amg_galerkin(nf, (long long)amg_h[k].col.size(), amg_d[k]->cptr.p,
-                                   amg_d[k]->csrc.p, amg_d[k - 1]->v.p, amg_d[k]->v.p, stream);
-    for (int k = 0; k + 1 < K && e == hipSuccess; k++)
-      e = pnp::launch_amg_dinv(nf, amg_d[k]->nb, amg_d[k]->dpos.p, amg_d[k]->v.p,
-                               amg_d[k]->dinv.p, stream);
-    for (int k = 0; k + 1 < K && e == hipSuccess; k++)
-      if (amg_d[k]->vf.p)
-        e = pnp::launch_amg_to_f32((long long)amg_d[k]->col.n * nf * nf, amg_d[k]->v.p,
-                                   amg_d[k]->vf.p, stream);
-    if (e == hipSuccess)
-      e = pnp::launch_amg_coarse_dense(nf, amg_d[K - 1]->nb, amg_d[K - 1]->rp.p,
-                                       amg_d[K - 1]->col.p, amg_d[K - 1]->v.p, amg_ainv.p, stream);
-    if (e != hipSuccess) return hipfail(e, "amg setup");
-    {  // coarsest inverse in place: LU with partial pivoting, then the inverse -- of A^T column-
-       // major, which leaves A^-1 row-major for k_coarse_apply
-      if (!blas) {
-        if (rocblas_create_handle(&blas) != rocblas_status_success)
-          return fail(PNP_E_HIP, "rocblas_create_handle failed");
-      }
-      if (rocblas_set_stream(blas, stream) != rocblas_status_success)
-        return fail(PNP_E_HIP, "rocblas_set_stream failed");
-      const int nc = amg_d[K - 1]->nb * nf;
-      if (rocsolver_dgetrf(blas, nc, nc, amg_ainv.p, nc, amg_ipiv.p, amg_info.p) !=
-              rocblas_status_success ||
-          rocsolver_dgetri(blas, nc, amg_ainv.p, nc, amg_ipiv.p, amg_info.p) !=
-              rocblas_status_success)
-        return fail(PNP_E_HIP, "rocsolver getrf/getri of the AMG coarsest level failed");
-      int info = 0;
-      e = hipMemcpyAsync(&info, amg_info.p, sizeof info, hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return hipfail(e, "amg setup");
-      if (info != 0)
-        return fail(PNP_E_STATE, "AMG: coarsest matrix singular (getrf info " +
-                                     std::to_string(info) + ")");
-      if (amg_ainv_f.p &&
-          (e = pnp::launch_amg_inverse_to_f32(nc, amg_ld, amg_ainv.p, amg_ainv_f.p, stream)) !=
-              hipSuccess)
-        return hipfail(e, "amg setup");
-    }
-    te(T_FACT, t0);
-    amg_setup_ms = (now_s() - ts) * 1e3;  // host-side issue time (device time: T_FACT timers)
-    amg_valid = true;
-    return PNP_OK;
-  }
-
-  // block-Jacobi sweeps on coarse level k + 1 (amg_d[k]): the configured count; PNP_AMG_DEEP_SWEEPS
-  // (A/B, environment) overrides it below level 1, where the kernels sit at the launch floor
-  int amg_sweeps(int k) const {
-    static const int deep = [] {
-      const char *e = std::getenv("PNP_AMG_DEEP_SWEEPS");
-      return e ? std::atoi(e) : 0;
-    }();
-    return (k >= 1 && deep >= 1) ? deep : amg_opts.coarse_sweeps;
-  }
-
-  // one V-cycle: vout = B d (owned rows); see amg.hip for the kernels
-  int amg_apply(const double *d, double *vout) {
-    const int K = int(amg_d.size()), sm = amg_opts.smoother, n = L.n_owned;
-    const double om = amg_opts.omega;
-    const long long nn = nown();
-    int rc, nsp = 0;
-    hipError_t e;
-    // level 0 pre-smoothing from zero, residual (SpMV residual mode), restriction (+ level-1
-    // pre-smoothing); without level-0 pre-smoothing x0 = 0 and the restriction takes d itself
-    // amg_opts.level0_presmooth: 1 always, 0 never, -1 (auto) only when the V-cycle must stay
-    // symmetric (CG, or a bare pnp_prec_apply); BiCGSTAB takes the post-smoothing-only cycle
-    const bool pre0 = amg_opts.level0_presmooth > 0 ||
-                      (amg_opts.level0_presmooth < 0 && amg_symmetric);
-    if (pre0) {
-      if ((rc = smoother(sm, d, amg_x0.p))) return rc;
-      e = pnp::launch_spmv(dl, nf, pat, vals.p, amg_x0.p, amg_t.p, 3, d, partials.p, &nsp,
-                           stream);
-    } else {
-      e = hipSuccess;  // x0 = 0: the restriction takes d, the prolongation no x0
-    }
-    if (e == hipSuccess)
-      e = pnp::launch_amg_restrict(nf, amg_d[0]->nb, amg_d[0]->mptr.p, amg_d[0]->mem.p,
-                                   pre0 ? amg_t.p : d, nullptr, amg_d[0]->b.p, amg_d[0]->dinv.p,
-                                   om, K > 1 ? amg_d[0]->x.p : nullptr, stream);
-    for (int k = 0; k + 1 < K && e == hipSuccess; k++) {
-      AmgDev &C = *amg_d[k], &N = *amg_d[k + 1];
-      for (int sw = 1; sw < amg_sweeps(k) && e == hipSuccess; sw++) {  // more pre-smoothing
-        e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, nullptr, C.x.p,
-                                 nullptr, C.b.p, C.dinv.p, om, C.x2.p, stream);
-        std::swap(C.x.p, C.x2.p);
-      }
-      // residual of level k+1 into its x2 (free until its post-smoothing), then restriction
-      if (e == hipSuccess)
-        e = pnp::launch_amg_resid(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, C.x.p, C.b.p,
-                                  C.x2.p, stream);
-      if (e == hipSuccess)
-        e = pnp::launch_amg_restrict(nf, N.nb, N.mptr.p, N.mem.p, C.x2.p, nullptr, N.b.p,
-                                     N.dinv.p, om, k + 2 < K ? N.x.p : nullptr, stream);
-    }
-    if (e == hipSuccess)
-      e = amg_ainv_f.p
-              ? pnp::launch_amg_coarse_apply_f32(amg_d[K - 1]->nb * nf, amg_ld, amg_ainv_f.p,
-                                                 amg_d[K - 1]->b.p, amg_d[K - 1]->x.p, stream)
-              : pnp::launch_amg_coarse_apply(amg_d[K - 1]->nb * nf, amg_ainv.p, amg_d[K - 1]->b.p,
-                                       amg_d[K - 1]->x.p, stream);
-    const double *res = amg_d[K - 1]->x.p;  // the solution of the level just finished
-    for (int k = K - 2; k >= 0 && e == hipSuccess; k--) {
-      AmgDev &C = *amg_d[k];
-      e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, amg_d[k + 1]->agg.p,
-                               C.x.p, res, C.b.p, C.dinv.p, om, C.x2.p, stream);
-      res = C.x2.p;
-      for (int sw = 1; sw < amg_sweeps(k) && e == hipSuccess; sw++) {  // more post-smoothing
-        double *out = res == C.x2.p ? C.x.p : C.x2.p;
-        e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, nullptr, res,
-                                 nullptr, C.b.p, C.dinv.p, om, out, stream);
-        res = out;
-      }
-    }
-    // level 0: prolongation, post-smoothing x += M^{-1} (d - A x)
-    if (e == hipSuccess)
-      e = pnp::launch_amg_prolong0(nf, n, amg_d[0]->agg.p, pre0 ? amg_x0.p : nullptr, res,
-                                   amg_y.p, stream);
-    if (e == hipSuccess)
-      e = pnp::launch_spmv(dl, nf, pat, vals.p, amg_y.p, amg_r.p, 3, d, partials.p, &nsp, stream);
-    if (e != hipSuccess) return hipfail(e, "amg v-cycle");
-    if (sm == PNP_PREC_ILU0) {  // vout = y + M^-1 r, written by the backward sweep
-      e = pnp::launch_ilu0_apply(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, amg_r.p,
-                                 amg_z.p, stream, 0, amg_y.p, vout, f32_now(), ilu_y32());
-      return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
-    }
-    if ((rc = smoother(sm, amg_r.p, amg_z.p))) return rc;
-    e = pnp::launch_axpby(nn, 1.0, amg_y.p, 1.0, amg_z.p, vout, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
-  }
-
-  // the single-level preconditioners, untimed, prerequisites (split / factors) in place
-  int smoother(int prec, const double *d, double *vout) {
-    hipError_t e = hipSuccess;
-    if (prec == PNP_PREC_JACOBI && mf_lin && vals_stale) {
-      // no SELL values: the diagonal blocks of jacobi_prepare(), one slot per chunk
-      if (!mf_diag_valid) return fail(PNP_E_STATE, "Jacobi: no diagonal (jacobi_prepare)");
-      pnp::DevLayout dv = dl;
-      dv.chunk_off = mf_choff.p;
-      e = pnp::launch_jacobi(dv, nf, pat, mf_diag.p, d, vout, stream);
-    } else if (prec == PNP_PREC_JACOBI) {
-      e = pnp::launch_jacobi(dl, nf, pat, vals.p, d, vout, stream);
-    } else if (prec == PNP_PREC_SSOR) {
-      e = pnp::launch_sgs(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, d, vout, tsgs.p,
-                          stream);
-    } else if (prec == PNP_PREC_ILU0) {
-      return ilu_apply(d, vout, 0, "preconditioner");
-    } else if (prec == PNP_PREC_SSOR_NATURAL) {
-      e = ssor_natural(d, vout);
-    } else {
-      e = hipMemcpyAsync(vout, d, sizeof(double) * nown(), hipMemcpyDeviceToDevice, stream);
-    }
-    return e == hipSuccess ? PNP_OK : hipfail(e, "preconditioner");
-  }
-
-  // v = M^{-1} d over owned rows (v sized n_local)
-  int precond(int prec, const double *d, double *vout) {
-    int rc;
-    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
-    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
-    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
-    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
-    hipEvent_t t0 = tb(T_PREC);
-    if (prec == PNP_PREC_AMG) {
-      if ((rc = amg_apply(d, vout))) return rc;
-      te(T_PREC, t0);
-      return PNP_OK;
-    }
-    if ((rc = smoother(prec, d, vout))) return rc;
-    te(T_PREC, t0);
-    return PNP_OK;
-  }
-
-  // BiCGSTAB on J zout = bdev (owned rows), zout zero start.  fixed > 0: exactly that many
-  // iterations, no convergence stop (reduction 0), used by the benchmarks.
-  int bicgstab(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res,
-               int fixed) {
-    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
-    double t_start = now_s();
-    long long n = nown();
-    int np = pnp::blas_nparts(n);
-    int rows_np = (L.n_owned + 255) / 256;
-    (void)rows_np;
-    hipError_t e;
-    e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(rs.p + 0, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(rt.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(v.p, 0, sizeof(double) * n, stream);
-    if (e == hipSuccess) e = hipMemsetAsync(p.p, 0, sizeof(double) * n, stream);
-    if (e != hipSuccess) return hipfail(e, "bicgstab init");
-    // set reduction, reset flags
-    pnp::Scalars &init = hS[2];  // pinned staging slot
-    std::memset(&init, 0, sizeof init);
-    init.reduction = fixed > 0 ? 0.0 : o.reduction;
-    // divergence guard for the AMG preconditioner only (a non-symmetric V-cycle can make
-    // BiCGSTAB diverge; ISTL semantics otherwise: run to maxit)
-    init.divguard = (o.prec == PNP_PREC_AMG && fixed <= 0) ? 1 : 0;
-    e = hipMemcpyAsync(S.p, &init, sizeof init, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "bicgstab scalars");
-    hipEvent_t t0 = tb(T_BLAS);
-    e = pnp::launch_dot(n, rs.p, rs.p, 0, partials.p, stream);
-    if (e != hipSuccess) return hipfail(e, "bicgstab norm0");
-    int rc = reduce_derive(np, 1, 0);
-    if (rc) return rc;
-    te(T_BLAS, t0);
-    int maxit = fixed > 0 ? fixed : o.maxit;
-    int check = o.check_every > 0 ? o.check_every : 8;
-    if (fixed > 0) check = fixed;
-    int prec = o.prec;
-    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
-    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
-    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
-    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
-    int nsp = 0, npu = 0;
-    // ILU(0): the two vector updates that feed the preconditioner also do colour 0 of its
-    // forward sweep (launch_update_fwd0); PNP_FUSE=0 keeps them apart (A/B)
-    static const bool fuse_env = [] {
-      const char *ev = std::getenv("PNP_FUSE");
-      return !(ev && std::atoi(ev) == 0);
-    }();
-    const bool fuse = fuse_env && prec == PNP_PREC_ILU0 && L.color_ptr.size() > 2;
-    const int c0_end = L.color_ptr.size() > 1 ? L.color_ptr[1] : 0;
-    // the colour launches record the timer events themselves: the first launch's start and the
-    // last launch's end (no marker dispatch in the measured span)
-    auto ilu_from1 = [&](const double *d, double *out) -> int {
-      hipEvent_t t0 = nullptr, t1 = nullptr;
-      if (timing && L.n_owned > 0) {
-        t0 = ev_get();
-        t1 = ev_get();
-      }
-      const int rc1 = ilu_apply(d, out, 1, "preconditioner", t0, t1);
-      if (rc1) return rc1;
-      if (t1) {
-        ev_pending[T_PREC].push_back({t0, t1});
-        t_n[T_PREC]++;
-      }
-      return PNP_OK;
-    };
-    // two-reduction iteration (two allreduces per iteration instead of three: rho_new from the
-    // same reduction as omega, the second half step's test lagged into the next h reduction):
-    // on by default with more than one rank, where each reduction is an allreduce round trip;
-    // PNP_OPT_BICG_TWORED (or PNP_BICG_TWORED) 0/1 forces it off/on.  Half-step counts keep
-    // ISTL's semantics.
-    const bool twored = twored_opt >= 0 ? twored_opt == 1 : dist;
-    // fused ILU(0), one reduction per half step: the first half step's x += alpha y is applied by
-    // the second half's update (one read and write of x per iteration fewer; the second
-    // preconditioned vector then goes to y2).  PNP_XDEFER=0 keeps the two passes (A/B).
-    static const bool xdefer_env = [] {
-      const char *ev = std::getenv("PNP_XDEFER");
-      return !(ev && std::atoi(ev) == 0);
-    }();
-    const bool xdefer = xdefer_env && fuse && !twored;
-    double *const y2p = xdefer ? y2.p : y.p;
-    int pending_np = 0;
-    // one BiCGSTAB iteration; for k >= 1 (and without the two-reduction variant's host state) it
-    // launches the same kernels with the same arguments every time, which is what the graph
-    // replay below relies on
-    auto body = [&](int k) -> int {
-      // p = r + beta (p - omega v)
-      hipEvent_t t0 = tb(T_BLAS);
-      if (fuse)
-        e = pnp::launch_update_fwd0(dl, nf, pat, c0_end, S.p, 0, k == 0 ? 1 : 0, nullptr, nullptr,
-                                    rs.p, v.p, p.p, uvals.p, y.p, nullptr, nullptr, stream,
-                                    f32_now(), nullptr, ilu_y32());
-      else
-        e = pnp::launch_update_p(n, S.p, rs.p, v.p, p.p, k == 0 ? 1 : 0, stream);
-      if (e != hipSuccess) return hipfail(e, "update_p");
-      te(T_BLAS, t0);
-      // y = M^{-1} p ; v = A y ; h = <rt, v>
-      const double *yin = p.p;
-      if (fuse) {
-        if ((rc = ilu_from1(p.p, y.p))) return rc;
-        yin = y.p;
-      } else if (prec != PNP_PREC_NONE) {
-        if ((rc = precond(prec, p.p, y.p))) return rc;
-        yin = y.p;
-      }
-      if ((rc = halo_spmv(const_cast<double *>(yin), v.p, 1, rt.p, nullptr, &nsp))) return rc;
-      if (twored)  // h, with the previous iteration's second-half test (||r||^2 in partials2)
-        rc = pending_np > 0 ? reduce_derive2(nsp, 1, pending_np, 1, 31) : reduce_derive(nsp, 1, 31);
-      else
-        rc = reduce_derive(nsp, 1, 1);
-      if (rc) return rc;
-      // x += alpha y ; r -= alpha v ; ||r|| (partials2: its half-step test is derived together
-      // with omega below -- one reduction and one allreduce fewer per iteration; the second
-      // half's kernels ignore a converged first half, update_xr skips on S->done).  Two-reduction
-      // iteration (twored): also <rt, s> into partials2, for rho_new without a third reduction.
-      t0 = tb(T_BLAS);
-      if (fuse)
-        e = pnp::launch_update_fwd0(dl, nf, pat, c0_end, S.p, 1, 0, xdefer ? nullptr : zout, yin,
-                                    rs.p, v.p, nullptr, uvals.p, y2p, partials2.p, &npu, stream,
-                                    f32_now(), twored ? rt.p : nullptr, ilu_y32());
-      else
-        e = pnp::launch_update_xr(n, S.p, 0, zout, yin, rs.p, v.p, twored ? rt.p : nullptr,
-                                  partials2.p, stream);
-      if (e != hipSuccess) return hipfail(e, "update x r (1)");
-      te(T_BLAS, t0);
-      // y = M^{-1} r ; t = A y ; <t,r>, <t,t> (twored: and <t,rt>)
-      const double *yin2 = rs.p;
-      if (fuse) {
-        if ((rc = ilu_from1(rs.p, y2p))) return rc;
-        yin2 = y2p;
-      } else if (prec != PNP_PREC_NONE) {
-        if ((rc = precond(prec, rs.p, y.p))) return rc;
-        yin2 = y.p;
-      }
-      if ((rc = halo_spmv(const_cast<double *>(yin2), t.p, twored ? 4 : 2, rs.p, rt.p, &nsp)))
-        return rc;
-      if (twored) {
-        if ((rc = reduce_derive2(nsp, 3, fuse ? npu : np, 2, 32))) return rc;
-        // x += omega y ; r -= omega t ; ||r||^2 into partials2, tested at the next h (stage 31)
-        t0 = tb(T_BLAS);
-        e = pnp::launch_update_xr(n, S.p, 1, zout, yin2, rs.p, t.p, nullptr, partials2.p, stream);
-        if (e != hipSuccess) return hipfail(e, "update x r (2)");
-        te(T_BLAS, t0);
-        pending_np = np;
-      } else {
-        if ((rc = reduce_derive2(nsp, 2, fuse ? npu : np, 1, 23))) return rc;
-        // x += omega y ; r -= omega t ; ||r||, <rt, r>
-        t0 = tb(T_BLAS);
-        e = pnp::launch_update_xr(n, S.p, 1, zout, yin2, rs.p, t.p, rt.p, partials.p, stream,
-                                  xdefer ? yin : nullptr);
-        if (e != hipSuccess) return hipfail(e, "update x r (2)");
-        if ((rc = reduce_derive(np, 2, 4))) return rc;
-        te(T_BLAS, t0);
-      }
-      if (debug_trace) {
-        e = hipMemcpyAsync(hS, S.p, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        std::fprintf(stderr,
-                     "bicgstab it=%d it_half=%.1f rho=%.6e rho_new=%.6e alpha=%.6e omega=%.6e "
-                     "h=%.6e norm=%.6e done=%d bd=%d\n",
-                     k + 1, hS->it_half, hS->rho, hS->rho_new, hS->alpha, hS->omega, hS->h,
-                     hS->norm, hS->done, hS->breakdown);
-      }
-      return PNP_OK;
-    };
-    // the iterations between two polls of the device scalars (every `check`): eagerly, or as one
-    // hipGraph replay (small systems, where launching ~20 kernels per iteration from the host
-    // costs more than running them: PNP_OPT_GRAPH)
-    bool graphs = use_graphs() && !dist && !twored && !debug_trace && !timing &&
-                  prec != PNP_PREC_AMG && !graphs_failed;
-    for (int k = 0; k < maxit;) {
-      const int kend = std::min(maxit, (k / check + 1) * check);  // next poll
-      if (k == 0) {
-        if ((rc = body(0))) return rc;
-        k = 1;
-      }
-      // whole graph blocks of glen iterations (one captured graph per block length, replayed as
-      // often as the poll interval holds it), the remainder eagerly; a capture or instantiation
-      // failure turns graphs off for the rest of the solve (eager launches, same results)
-      const int glen = std::min(check, 16);
-      while (graphs && glen > 1 && kend - k >= glen) {
-        const GraphKey key{glen, prec, fuse ? 1 : 0, nf, pat, f32_now() + (ilu_y32() ? 4 : 0),
-                           ilu_flow_opt * 4 + (nat_flow_opt + 1),
-                           mf_lin ? (vals_stale ? 2 : 1) : 0, zout, dl.dmask, graph_epoch};
-        bool captured = true;
-        rc = graph_run(key, [&]() -> int {
-          for (int i = 0; i < key.count; i++)
-            if (int r2 = body(1)) return r2;
-          return PNP_OK;
-        }, &captured);
-        if (rc && !captured) {  // the graph path failed before anything ran: eager from here
-          graphs_failed = true;
-          graphs = false;
-          break;
-        }
-        if (rc) return rc;
-        k += glen;
-      }
-      for (; k < kend; k++)
-        if ((rc = body(k))) return rc;
-      e = hipMemcpyAsync(hS, S.p, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-      if (e == hipSuccess) e = hipStreamSynchronize(stream);
-      if (e != hipSuccess) return hipfail(e, "bicgstab poll");
-      if (hS->done) break;
-    }
-    if (twored && pending_np > 0 && (rc = reduce_derive(pending_np, 1, 33, true))) return rc;
-    e = hipMemcpyAsync(hS, S.p, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "bicgstab result");
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
-    if (prec == PNP_PREC_ILU0 && (rc = ilu_flow_check())) return rc;
-    double it = std::min(double(maxit), hS->it_half);
-    res.converged = hS->done == 1 ? 1 : 0;
-    res.breakdown = hS->breakdown;
-    res.it_half = it;
-    res.iterations = int(std::ceil(it));
-    res.defect0 = hS->norm0;
-    res.defect = hS->norm;
-    res.reduction = hS->norm0 > 0 ? hS->norm / hS->norm0 : 0.0;
-    res.elapsed = now_s() - t_start;
-    return PNP_OK;
-  }
-
-  // ISTL CGSolver on J zout = bdev (owned rows), zout zero start; device-resident scalars
-  // (derive stages 10-14).  iterations = matrix-vector products.
-  int cg(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res) {
-    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
-    double t_start = now_s();
-    long long n = nown();
-    int np = pnp::blas_nparts(n);
-    int prec = o.prec, nsp = 0, rc;
-    hipError_t e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(rs.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "cg init");
-    pnp::Scalars &init = hS[2];
-    std::memset(&init, 0, sizeof init);
-    init.reduction = o.reduction;
-    e = hipMemcpyAsync(S.p, &init, sizeof init, hipMemcpyHostToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "cg scalars");
-    if ((e = pnp::launch_dot(n, rs.p, rs.p, 0, partials.p, stream)) != hipSuccess)
-      return hipfail(e, "cg norm0");
-    if ((rc = reduce_derive(np, 1, 10))) return rc;
-    if ((rc = precond(prec, rs.p, p.p))) return rc;  // p = M^{-1} r
-    if ((e = pnp::launch_dot(n, p.p, rs.p, 0, partials.p, stream)) != hipSuccess)
-      return hipfail(e, "cg rho");
-    if ((rc = reduce_derive(np, 1, 11))) return rc;
-    int check = o.check_every > 0 ? o.check_every : 8;
-    for (int k = 0; k < o.maxit; k++) {
-      if ((rc = halo_spmv(p.p, v.p, 1, p.p, nullptr, &nsp))) return rc;
-      hipEvent_t t0 = nullptr;
-      if ((rc = reduce_derive(nsp, 1, 12))) return rc;
-      t0 = tb(T_BLAS);
-      e = pnp::launch_update_xr(n, S.p, 0, zout, p.p, rs.p, v.p, nullptr, partials.p, stream);
-      if (e != hipSuccess) return hipfail(e, "cg update");
-      if ((rc = reduce_derive(np, 1, 13))) return rc;
-      te(T_BLAS, t0);
-      if ((k + 1) % check == 0 || k + 1 == o.maxit) {
-        e = hipMemcpyAsync(hS, S.p, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(stream);
-        if (e != hipSuccess) return hipfail(e, "cg poll");
-        if (hS->done) break;
-      }
-      if ((rc = precond(prec, rs.p, y.p))) return rc;  // q = M^{-1} r
-      t0 = tb(T_BLAS);
-      if ((e = pnp::launch_dot(n, y.p, rs.p, 0, partials.p, stream)) != hipSuccess)
-        return hipfail(e, "cg rho'");
-      if ((rc = reduce_derive(np, 1, 14))) return rc;
-      if ((e = pnp::launch_cg_update_p(n, S.p, y.p, p.p, stream)) != hipSuccess)
-        return hipfail(e, "cg p");
-      te(T_BLAS, t0);
-    }
-    e = hipMemcpyAsync(hS, S.p, sizeof(pnp::Scalars), hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "cg result");
-    if (o.prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
-    res.converged = hS->done == 1 ? 1 : 0;
-    res.breakdown = 0;
-    res.iterations = hS->iter;
-    res.it_half = hS->iter;
-    res.defect0 = hS->norm0;
-    res.defect = hS->norm;
-    res.reduction = hS->norm0 > 0 ? hS->norm / hS->norm0 : 0.0;
-    res.elapsed = now_s() - t_start;
-    return PNP_OK;
-  }
-
-  // Restarted GMRES(m) (flexible: the preconditioned basis Z is kept, x = x0 + Z y) on
-  // J zout = bdev (owned rows), zero start, right-preconditioned: the monitored norm is the true
-  // residual's.  DESIGN.md 4.8.  The state (Hessenberg matrix, rotations, history, flags) lives on
-  // the device (gmres_small.h); the host enqueues Arnoldi steps and reads the state's header only
-  // at the check_every poll.  A cycle ends on the device (phase 1: the step kernels idle) when the
-  // estimate meets the test, at the restart length or at maxit; the host enqueues the cycle end
-  // (x update, r = b - A x, the true norm, the next cycle's V_0) where it knows a cycle is over:
-  // after m steps, or after a poll that shows phase 1.  Until then the preconditioner and the
-  // SpMV of the enqueued steps run on vectors nobody reads.
-  int gmres_alloc(bool flexible) {
-    const size_t ld = (size_t(nf) * size_t(dl.n_local) + 1) & ~size_t(1);
-    const int m = gm_restart;
-    hipError_t e = hipSuccess;
-    if (gm_V.n != ld * size_t(m + 1)) e = gm_V.alloc(ld * size_t(m + 1));
-    if (e == hipSuccess && flexible && gm_Z.n != ld * size_t(m)) e = gm_Z.alloc(ld * size_t(m));
-    const size_t nps = size_t(pnp::gmres_nparts(nown()));
-    if (e == hipSuccess && gm_part.n != nps * (pnp::kGmMaxRestart + 2))
-      e = gm_part.alloc(nps * (pnp::kGmMaxRestart + 2));
-    if (e == hipSuccess && !gm_S.p) e = gm_S.alloc(1);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "gmres basis");
-  }
-  void gmres_free() {
-    gm_V.release();
-    gm_Z.release();
-    gm_part.release();
-  }
-
-  int gmres(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res,
-            bool flexible) {
-    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
-    if (o.maxit < 0) return fail(PNP_E_ARG, "maxit must not be negative");
-    static_assert(offsetof(pnp::GmresState, red1) <= sizeof(pnp::Scalars), "poll staging");
-    const size_t hdr = offsetof(pnp::GmresState, red1);
-    double t_start = now_s();
-    const long long n = nown();
-    const int m = gm_restart, prec = o.prec;
-    if (prec == PNP_PREC_NONE) flexible = false;  // Z = V
-    int rc;
-    if ((rc = gmres_alloc(flexible))) return rc;
-    const long long ld = (long long)((size_t(nf) * size_t(dl.n_local) + 1) & ~size_t(1));
-    const int nps = pnp::gmres_nparts(n);
-    hipError_t e = hipSuccess;
-    // the history keeps the first kGmHistCap steps: a "no limit" maxit must not size a buffer
-    const int hcap = std::min(o.maxit, pnp::kGmHistCap);
-    if (gm_hist.n < size_t(hcap) + 2) e = gm_hist.alloc(size_t(hcap) + 2);
-    if (e != hipSuccess) return hipfail(e, "gmres history");
-    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
-    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
-    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
-    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
-    pnp::GmresState *St = gm_S.p;
-    pnp::GmresState *hp = reinterpret_cast<pnp::GmresState *>(hS);  // header only
-    {
-      pnp::GmresState *init = reinterpret_cast<pnp::GmresState *>(hS + 2);
-      std::memset(init, 0, hdr);
-      init->reduction = o.reduction;
-      init->m = m;
-      init->maxit = o.maxit;
-      init->phase = 1;  // the start is a cycle end with no columns
-      init->hcap = hcap;
-      e = hipMemcpyAsync(St, init, hdr, hipMemcpyHostToDevice, stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(rs.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "gmres init");
-    auto V = [&](int i) { return gm_V.p + size_t(i) * size_t(ld); };
-    auto Z = [&](int i) { return gm_Z.p + size_t(i) * size_t(ld); };
-    auto allred = [&](double *d, int k) -> int {
-      if (!dist) return PNP_OK;
-      hipEvent_t t0 = tb(T_ALLRED);
-      int r2 = allreduce_dev(d, k);
-      if (r2) return r2;
-      te(T_ALLRED, t0);
-      return PNP_OK;
-    };
-    // ||rs||, the true norm's test, V_0 of the next cycle
-    auto close_cycle = [&](int first) -> int {
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_gmres_norm2(St, rs.p, n, gm_part.p, nps, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "gmres norm");
-      te(T_BLAS, t0);
-      int r2 = allred(St->red3, 1);
-      if (r2) return r2;
-      t0 = tb(T_BLAS);
-      e2 = pnp::launch_gmres_restart(St, gm_hist.p, first, gm_V.p, ld, n, rs.p, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "gmres restart");
-      te(T_BLAS, t0);
-      return PNP_OK;
-    };
-    auto cycle_end = [&]() -> int {
-      int nsp = 0, r2;
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_gmres_backsub(St, stream);
-      if (e2 == hipSuccess) {
-        if (flexible)  // x += Z y
-          e2 = pnp::launch_gmres_combine(St, gm_Z.p, ld, n, zout, 1, stream);
-        else if (prec == PNP_PREC_NONE)  // x += V y
-          e2 = pnp::launch_gmres_combine(St, gm_V.p, ld, n, zout, 1, stream);
-        else  // t = V y
-          e2 = pnp::launch_gmres_combine(St, gm_V.p, ld, n, t.p, 0, stream);
-      }
-      if (e2 != hipSuccess) return hipfail(e2, "gmres update");
-      te(T_BLAS, t0);
-      if (!flexible && prec != PNP_PREC_NONE) {  // x += M^-1 t
-        if ((r2 = precond(prec, t.p, y.p))) return r2;
-        t0 = tb(T_BLAS);
-        if ((e2 = pnp::launch_gmres_xpy(St, zout, y.p, n, stream)) != hipSuccess)
-          return hipfail(e2, "gmres update");
-        te(T_BLAS, t0);
-      }
-      if ((r2 = halo_spmv(zout, rs.p, 3, bdev, nullptr, &nsp))) return r2;  // r = b - A x
-      return close_cycle(0);
-    };
-    // one Arnoldi step with the host's column index hj (the device's own j while it steps)
-    auto step = [&](int hj) -> int {
-      int nsp = 0, r2;
-      double *in = V(hj);
-      if (prec != PNP_PREC_NONE) {
-        in = flexible ? Z(hj) : y.p;
-        if ((r2 = precond(prec, V(hj), in))) return r2;
-      }
-      if ((r2 = halo_spmv(in, V(hj + 1), 0, nullptr, nullptr, &nsp))) return r2;
-      double *red[3] = {St->red1, St->red2, St->red3};
-      const int cnt[3] = {hj + 2, hj + 1, 1};
-      for (int pass = 0; pass < 3; pass++) {
-        hipEvent_t t0 = tb(T_BLAS);
-        hipError_t e2 = pnp::launch_gmres_orth(pass, St, gm_V.p, ld, n, gm_part.p, nps, hj, stream);
-        if (e2 != hipSuccess) return hipfail(e2, "gmres orthogonalisation");
-        te(T_BLAS, t0);
-        if ((r2 = allred(red[pass], cnt[pass]))) return r2;
-      }
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_gmres_hess(St, gm_hist.p, gm_V.p, ld, n, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "gmres hessenberg");
-      te(T_BLAS, t0);
-      return PNP_OK;
-    };
-    auto poll = [&]() -> int {
-      hipError_t e2 = hipMemcpyAsync(hp, St, hdr, hipMemcpyDeviceToHost, stream);
-      if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "gmres poll");
-    };
-    if ((rc = close_cycle(1))) return rc;
-    const int check = o.check_every > 0 ? o.check_every : 8;
-    int hj = 0, it_known = 0;
-    if ((rc = poll())) return rc;
-    while (!hp->done) {
-      // steps until the next poll: never past the restart length or maxit, and one at a time
-      // once the estimate is within a decade of the target (a step enqueued after the device has
-      // ended the cycle costs a whole preconditioner application and an SpMV for nothing)
-      const bool near = hp->norm < 10.0 * o.reduction * hp->norm0;
-      const int ns = std::max(1, std::min({near ? 1 : check, m - hj, o.maxit - it_known}));
-      for (int q = 0; q < ns; q++, hj++)
-        if ((rc = step(hj))) return rc;
-      if (hj == m) {  // the device's cycle is over at the latest now
-        if ((rc = cycle_end())) return rc;
-        hj = 0;
-      }
-      if ((rc = poll())) return rc;
-      if (hp->done) break;
-      if (hp->phase == 1) {  // ended early on the device: estimate met, maxit or breakdown
-        if ((rc = cycle_end())) return rc;
-        hj = 0;
-        if ((rc = poll())) return rc;
-      }
-      it_known = hp->it;
-    }
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
-    if (prec == PNP_PREC_ILU0 && (rc = ilu_flow_check())) return rc;
-    gm_history.assign(size_t(std::min(hp->it, hcap)) + 1, 0.0);
-    e = hipMemcpyAsync(gm_history.data(), gm_hist.p, sizeof(double) * gm_history.size(),
-                       hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "gmres history");
-    res.converged = hp->done == 1 ? 1 : 0;
-    res.breakdown = hp->breakdown;
-    res.iterations = hp->it;
-    res.it_half = hp->it;
-    res.defect0 = hp->norm0;
-    res.defect = hp->norm;
-    res.reduction = hp->norm0 > 0 ? hp->norm / hp->norm0 : 0.0;
-    res.elapsed = now_s() - t_start;
-    return PNP_OK;
-  }
-
-  // IDR(s), bi-orthogonal variant, on J zout = bdev (owned rows), zero start, right-preconditioned:
-  // the monitored norm is the true system's residual's.  DESIGN.md 4.10.  The state (M, f, c,
-  // alpha, beta, omega, counters, flags) lives on the device (idr_small.h); the host enqueues the
-  // fixed sequence step 0 .. s - 1, omega step, step 0, ... and reads the state's header only at
-  // the check_every poll.  When the recurrence's norm meets the test (or at maxit, or on a
-  // breakdown) the device enters phase 2 and every later step kernel idles; the host, once a poll
-  // shows it, forms r = b - A x and the device judges the true norm: stop, or go on from that
-  // residual with G = U = 0, M = I, omega = 1 (a residual replacement).
-  long long idr_ld(bool ghosts) const {
-    const size_t rows = ghosts ? size_t(dl.n_local) : size_t(L.n_owned);
-    return (long long)((size_t(nf) * rows + 1) & ~size_t(1));
-  }
-  void idr_free() {
-    idr_G.release();
-    idr_U.release();
-    idr_P.release();
-    idr_part.release();
-    idr_P_s = idr_P_nf = 0;
-  }
-  // the shadow matrix for the current s and field count: counter-based entries by global vertex,
-  // then modified Gram-Schmidt with one reduction (and allreduce) per dot product
-  int idr_shadow_build() {
-    const int s = idr_s;
-    if (idr_P_s == s && idr_P_nf == nf && idr_P.p) return PNP_OK;
-    const long long n = nown(), ldg = idr_ld(false);
-    const int nps = pnp::idr_nparts(n);
-    hipError_t e = hipSuccess;
-    idr_P_s = idr_P_nf = 0;
-    if (idr_P.n != size_t(ldg) * s) e = idr_P.alloc(size_t(ldg) * s);
-    if (e == hipSuccess && idr_part.n != size_t(nps) * (pnp::kIdrMaxS + 4))
-      e = idr_part.alloc(size_t(nps) * (pnp::kIdrMaxS + 4));
-    if (e == hipSuccess && !idr_S.p) e = idr_S.alloc(1);
-    if (e == hipSuccess)
-      e = pnp::launch_idr_shadow_fill(L.n_owned, nf, s, d_l2g.p, idr_P.p, ldg, stream);
-    if (e != hipSuccess) return hipfail(e, "idr shadow");
-    auto col = [&](int j) { return idr_P.p + size_t(j) * size_t(ldg); };
-    int rc;
-    for (int j = 0; j < s; j++) {
-      for (int i = 0; i <= j; i++) {  // i == j: the norm
-        e = pnp::launch_idr_dot(idr_S.p, col(i), col(j), n, idr_part.p, nps, stream);
-        if (e != hipSuccess) return hipfail(e, "idr shadow");
-        if ((rc = allreduce_dev(pnp::idr_red(idr_S.p), 1))) return rc;
-        e = pnp::launch_idr_mgs(idr_S.p, col(j), i < j ? col(i) : nullptr, n, stream);
-        if (e != hipSuccess) return hipfail(e, "idr shadow");
-      }
-    }
-    idr_P_s = s;
-    idr_P_nf = nf;
-    return PNP_OK;
-  }
-  int idr_alloc() {
-    const int s = idr_s;
-    const size_t ldg = size_t(idr_ld(false)), ldu = size_t(idr_ld(true));
-    hipError_t e = hipSuccess;
-    if (idr_G.n != ldg * s) e = idr_G.alloc(ldg * s);
-    if (e == hipSuccess && idr_U.n != ldu * s) e = idr_U.alloc(ldu * s);
-    if (e != hipSuccess) return hipfail(e, "idr arrays");
-    return idr_shadow_build();
-  }
-
-  int idr(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res) {
-    if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
-    if (o.maxit < 0) return fail(PNP_E_ARG, "maxit must not be negative");
-    static_assert(offsetof(pnp::IdrState, red) <= sizeof(pnp::Scalars), "poll staging");
-    const size_t hdr = offsetof(pnp::IdrState, red);
-    double t_start = now_s();
-    const long long n = nown();
-    const int s = idr_s, prec = o.prec;
-    int rc;
-    if ((rc = idr_alloc())) return rc;
-    const long long ldg = idr_ld(false), ldu = idr_ld(true);
-    const int nps = pnp::idr_nparts(n);
-    hipError_t e = hipSuccess;
-    const int hcap = std::min(o.maxit, pnp::kIdrHistCap);
-    if (idr_hist.n < size_t(hcap) + 2) e = idr_hist.alloc(size_t(hcap) + 2);
-    if (e != hipSuccess) return hipfail(e, "idr history");
-    if (prec == PNP_PREC_ILU0 && ((rc = ilu_factor()) || (rc = split(2)))) return rc;
-    if (prec == PNP_PREC_JACOBI && (rc = jacobi_prepare())) return rc;
-    if (prec == PNP_PREC_SSOR && (rc = split(1))) return rc;
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = csr_values())) return rc;
-    if (prec == PNP_PREC_AMG && (rc = amg_setup())) return rc;
-    pnp::IdrState *St = idr_S.p;
-    pnp::IdrState *hp = reinterpret_cast<pnp::IdrState *>(hS);  // header only
-    double *red = pnp::idr_red(St);
-    {
-      pnp::IdrState *init = reinterpret_cast<pnp::IdrState *>(hS + 2);
-      std::memset(init, 0, hdr);
-      init->reduction = o.reduction;
-      init->omega = 1.0;
-      init->s = s;
-      init->maxit = o.maxit;
-      init->phase = 2;  // the start is a judged residual like any other
-      init->hcap = hcap;
-      e = hipMemcpyAsync(St, init, hdr, hipMemcpyHostToDevice, stream);
-    }
-    if (e == hipSuccess) e = hipMemsetAsync(zout, 0, sizeof(double) * n, stream);
-    if (e == hipSuccess)
-      e = hipMemcpyAsync(rs.p, bdev, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-    if (e != hipSuccess) return hipfail(e, "idr init");
-    auto G = [&](int i) { return idr_G.p + size_t(i) * size_t(ldg); };
-    auto U = [&](int i) { return idr_U.p + size_t(i) * size_t(ldu); };
-    auto allred = [&](int k) -> int {
-      if (!dist) return PNP_OK;
-      hipEvent_t t0 = tb(T_ALLRED);
-      int r2 = allreduce_dev(red, k);
-      if (r2) return r2;
-      te(T_ALLRED, t0);
-      return PNP_OK;
-    };
-    auto small = [&](int which, int hk) -> int {
-      hipError_t e2 = pnp::launch_idr_small(St, idr_hist.p, which, hk, stream);
-      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "idr state");
-    };
-    // rs holds a true residual: its norm and P^T rs, the verdict, and a clean start if it goes on
-    auto begin = [&](int first) -> int {
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_idr_resid_dots(St, s, rs.p, idr_P.p, ldg, n, idr_part.p, nps, stream);
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(idr_G.p, 0, sizeof(double) * idr_G.n, stream);
-      if (e2 == hipSuccess) e2 = hipMemsetAsync(idr_U.p, 0, sizeof(double) * idr_U.n, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr residual");
-      te(T_BLAS, t0);
-      int r2 = allred(s + 1);
-      if (r2) return r2;
-      return small(4, first);
-    };
-    auto step = [&](int hk) -> int {
-      int nsp = 0, r2;
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_idr_v(St, hk, rs.p, idr_G.p, ldg, n, t.p, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr v");
-      te(T_BLAS, t0);
-      const double *vh = t.p;
-      if (prec != PNP_PREC_NONE) {
-        if ((r2 = precond(prec, t.p, y.p))) return r2;
-        vh = y.p;
-      }
-      t0 = tb(T_BLAS);
-      if ((e2 = pnp::launch_idr_u(St, hk, vh, idr_U.p, ldu, n, stream)) != hipSuccess)
-        return hipfail(e2, "idr u");
-      te(T_BLAS, t0);
-      if ((r2 = halo_spmv(U(hk), G(hk), 0, nullptr, nullptr, &nsp))) return r2;
-      t0 = tb(T_BLAS);
-      e2 = pnp::launch_idr_ptg(St, hk, s, idr_G.p, ldg, idr_P.p, n, idr_part.p, nps, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr shadow products");
-      te(T_BLAS, t0);
-      if ((r2 = allred(s))) return r2;
-      t0 = tb(T_BLAS);
-      if ((r2 = small(0, hk))) return r2;
-      e2 = pnp::launch_idr_update(St, hk, idr_G.p, ldg, idr_U.p, ldu, rs.p, zout, n, idr_part.p,
-                                  nps, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr update");
-      te(T_BLAS, t0);
-      if ((r2 = allred(1))) return r2;
-      return small(1, hk);
-    };
-    auto omega_step = [&]() -> int {
-      int nsp = 0, r2;
-      double *vh = rs.p;
-      if (prec != PNP_PREC_NONE) {
-        if ((r2 = precond(prec, rs.p, y.p))) return r2;
-        vh = y.p;
-      } else {  // the SpMV's input carries ghosts, which the exchange writes: not into rs
-        hipError_t e2 = hipMemcpyAsync(y.p, rs.p, sizeof(double) * n, hipMemcpyDeviceToDevice, stream);
-        if (e2 != hipSuccess) return hipfail(e2, "idr copy");
-        vh = y.p;
-      }
-      if ((r2 = halo_spmv(vh, t.p, 0, nullptr, nullptr, &nsp))) return r2;
-      hipEvent_t t0 = tb(T_BLAS);
-      hipError_t e2 = pnp::launch_idr_om_dots(St, t.p, rs.p, n, idr_part.p, nps, stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr omega");
-      te(T_BLAS, t0);
-      if ((r2 = allred(3))) return r2;
-      t0 = tb(T_BLAS);
-      if ((r2 = small(2, 0))) return r2;
-      e2 = pnp::launch_idr_om_update(St, s, t.p, vh, rs.p, zout, idr_P.p, ldg, n, idr_part.p, nps,
-                                     stream);
-      if (e2 != hipSuccess) return hipfail(e2, "idr omega update");
-      te(T_BLAS, t0);
-      if ((r2 = allred(s + 1))) return r2;
-      return small(3, 0);
-    };
-    auto poll = [&]() -> int {
-      hipError_t e2 = hipMemcpyAsync(hp, St, hdr, hipMemcpyDeviceToHost, stream);
-      if (e2 == hipSuccess) e2 = hipStreamSynchronize(stream);
-      return e2 == hipSuccess ? PNP_OK : hipfail(e2, "idr poll");
-    };
-    if ((rc = begin(1))) return rc;
-    const int check = o.check_every > 0 ? o.check_every : 8;
-    int hk = 0, it_known = 0;  // hk == s: the omega step is next
-    if ((rc = poll())) return rc;
-    while (!hp->done) {
-      // applications until the next poll: never past maxit, and one at a time once the norm is
-      // within a decade of the target (an application enqueued after the recurrence has ended
-      // costs a preconditioner application and an SpMV for nothing)
-      const bool near = hp->norm < 10.0 * o.reduction * hp->norm0;
-      const int ns = std::max(1, std::min(near ? 1 : check, o.maxit - it_known));
-      for (int q = 0; q < ns; q++) {
-        if ((rc = hk < s ? step(hk) : omega_step())) return rc;
-        hk = hk < s ? hk + 1 : 0;
-      }
-      if ((rc = poll())) return rc;
-      if (hp->done) break;
-      if (hp->phase == 2) {  // the recurrence has ended: the true residual decides
-        int nsp = 0;
-        if ((rc = halo_spmv(zout, rs.p, 3, bdev, nullptr, &nsp))) return rc;  // r = b - A x
-        if ((rc = begin(0))) return rc;
-        hk = 0;
-        if ((rc = poll())) return rc;
-      }
-      it_known = hp->it;
-    }
-    if (prec == PNP_PREC_SSOR_NATURAL && (rc = nat_check())) return rc;
-    if (prec == PNP_PREC_ILU0 && (rc = ilu_flow_check())) return rc;
-    gm_history.assign(size_t(std::min(hp->it, hcap)) + 1, 0.0);
-    e = hipMemcpyAsync(gm_history.data(), idr_hist.p, sizeof(double) * gm_history.size(),
-                       hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) return hipfail(e, "idr history");
-    idr_replacements += hp->replacements;
-    res.converged = hp->done == 1 ? 1 : 0;
-    res.breakdown = hp->breakdown;
-    res.iterations = hp->it;
-    res.it_half = hp->it;
-    res.defect0 = hp->norm0;
-    res.defect = hp->norm;
-    res.reduction = hp->norm0 > 0 ? hp->norm / hp->norm0 : 0.0;
-    res.elapsed = now_s() - t_start;
-    return PNP_OK;
-  }
-
-  // ---- reference-order mode (PNP_OPT_SEQ_ORDER) ------------------------------------------------
-  // The reference's single-rank arithmetic in its order (seq_order.hip): element-order assembly
-  // into the CSR view, ISTL's sequential mv / dot / updates, the scalar recurrences here in double.
-  // External-layout vectors throughout.  P1, one rank.
-  bool seq_on() const { return seq_opt && degree == 1 && !dist; }
-  int nseq() const { return nf * mesh.nv; }
-  enum { SQ_X = 0, SQ_R, SQ_Z, SQ_PREVU, SQ_P, SQ_V, SQ_T, SQ_Y, SQ_RT, SQ_B, SQ_N };
-  double *sq(int k) { return seq_vec.p + size_t(k) * size_t(3 * mesh.nv); }
-
-  int seq_build() {
-    if (seq_built) return PNP_OK;
-    const int nv = mesh.nv, nt = mesh.nt;
-    std::vector<int> vptr(nv + 1, 0), vinc(size_t(3) * nt);
-    for (int e = 0; e < nt; e++)
-      for (int a = 0; a < 3; a++) vptr[mesh.tri[3 * e + a] + 1]++;
-    for (int v = 0; v < nv; v++) vptr[v + 1] += vptr[v];
-    std::vector<int> fill(vptr.begin(), vptr.end() - 1);
-    for (int e = 0; e < nt; e++)  // ascending element index per vertex
-      for (int a = 0; a < 3; a++) vinc[fill[mesh.tri[3 * e + a]]++] = e << 2 | a;
-    int rc;
-    if ((rc = upv(seq_tri, mesh.tri, "seq tri")) || (rc = upv(seq_xy, mesh.xy, "seq xy")) ||
-        (rc = upv(seq_vptr, vptr, "seq vptr")) || (rc = upv(seq_vinc, vinc, "seq vinc")))
-      return rc;
-    hipError_t e;
-    if ((e = seq_vec.alloc(size_t(SQ_N) * 3 * nv)) != hipSuccess ||
-        (e = seq_dotv.alloc(2)) != hipSuccess || (e = seq_rl.alloc(size_t(9) * nt)) != hipSuccess ||
-        (e = seq_rlo.alloc(size_t(9) * nt)) != hipSuccess ||
-        (e = seq_rlt.alloc(size_t(9) * nt)) != hipSuccess ||
-        (e = seq_jl.alloc(size_t(81) * nt)) != hipSuccess ||
-        (e = seq_jlt.alloc(size_t(81) * nt)) != hipSuccess)
-      return hipfail(e, "seq buffers");
-    seq_built = true;
-    return PNP_OK;
-  }
-
-  // per operator: constrained rows, alpha_boundary's terms per (element, local index) in the order
-  // PDELab adds them into the element's local vector (the oracle's boundary_face statements: the
-  // element's faces in DUNE's order (0,1), (0,2), (1,2), each a boundary intersection when its edge
-  // is a boundary segment, run from its lower to its higher local vertex; 2-point Gauss; fields in
-  // order; every basis function of the element at the face point; rl += scale * (j * phi * factor)),
-  // frozen fields
-  int seq_prepare() {
-    int rc;
-    if ((rc = seq_build())) return rc;
-    if (seq_op_valid) return PNP_OK;
-    if (seq_cextra) return fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: pnp_op_args.c_extra is not supported");
-    const int nt = mesh.nt, nl = 3 * nf;
-    std::vector<std::vector<double>> terms(size_t(nt) * nl);
-    const bool bnd = kind == PNP_OP_PNP || kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_PB ||
-                     kind == PNP_OP_POISSON;
-    if (bnd) {
-      std::unordered_map<long long, int> seg;  // edge -> its (first) boundary segment
-      auto key = [](int a, int b) { return (long long)std::min(a, b) << 32 | unsigned(std::max(a, b)); };
-      for (int b = 0; b < mesh.nb; b++) seg.emplace(key(mesh.bseg[2 * b], mesh.bseg[2 * b + 1]), b);
-      static const int kFaceV[3][2] = {{0, 1}, {0, 2}, {1, 2}};
-      static const double corner[3][2] = {{0.0, 0.0}, {1.0, 0.0}, {0.0, 1.0}};
-      const double PI = params.pi;
-      const double scale = kind == PNP_OP_PNP_IMPLICIT_EULER ? seq_dt : 1.0;
-      const double gt[2] = {0.5 - 0.5 / std::sqrt(3.0), 0.5 + 0.5 / std::sqrt(3.0)};
-      for (int e = 0; e < nt && !seg.empty(); e++)
-        for (int k = 0; k < 3; k++) {
-          const int ia = kFaceV[k][0], ib = kFaceV[k][1];
-          const int va = mesh.tri[3 * e + ia], vb = mesh.tri[3 * e + ib];
-          const auto it = seg.find(key(va, vb));
-          if (it == seg.end()) continue;
-          const pnp::Surface &S = params.surf[mesh.bgroup[it->second]];
-          const double dx = mesh.xy[2 * vb] - mesh.xy[2 * va],
-                       dy = mesh.xy[2 * vb + 1] - mesh.xy[2 * va + 1];
-          const double len = std::sqrt(dx * dx + dy * dy);
-          for (int q = 0; q < 2; q++) {
-            double factor = 0.5 * len;
-            const double y = mesh.xy[2 * va + 1] + gt[q] * dy;
-            if (params.cylindrical) factor *= y * 2 * PI;
-            const double lx = corner[ia][0] + (corner[ib][0] - corner[ia][0]) * gt[q];
-            const double ly = corner[ia][1] + (corner[ib][1] - corner[ia][1]) * gt[q];
-            const double phi[3] = {1.0 - lx - ly, lx, ly};
-            for (int f = 0; f < nf; f++) {
-              if (S.btype(f) == 0) continue;  // isDirichlet
-              const double j = S.flux(f);
-              for (int i = 0; i < 3; i++)
-                terms[size_t(e) * nl + 3 * f + i].push_back(scale * (j * phi[i] * factor));
+      if (shared)  // every group's rows in level order (stable: a chain's rows stay in order)
+        for (auto &G : grows)
+          std::stable_sort(G.begin(), G.end(), [&](int a, int b) { return lev[a] < lev[b]; });
+      const int wpad = wmax;
+      if (wpad <= pnp::ssor_natural_chain_width()) {
+        std::vector<int> gptr(1, 0), ecode;
+        std::vector<int4> rec;
+        for (const auto &G : grows) {
+          const int H = pnp::ssor_natural_chain_history();
+          for (size_t t = 0; t < G.size(); t++) {
+            const int R = G[t];
+            const int len = cnt[R + 1] - cnt[R];
+            rec.push_back(make_int4(R, len | (diag[R] - cnt[R]) << 8, cnt[R], P(R)));
+            for (int k = 0; k < wpad; k++) {
+              if (k < len) {
+                const int C = col[cnt[R] + k];
+                const int fc = empty(C) ? -1 : fwd ? (C < R ? C : -1) : (C <= R ? C : -(C + 2));
+                // kind: 0 zero, 1 forward value, 2 backward value, 3 in the wave's registers
+                int code = fc == -1 ? 0 : fc >= 0 ? (fc << 2 | 1) : ((-(fc + 2)) << 2 | 2);
+                const bool fresh = fwd ? (code & 3) == 1 : (code & 3) == 2;  // this sweep's value
+                for (int h = 1; fresh && h <= H && size_t(h) <= t; h++)
+                  if (G[t - h] == C) {
+                    code = h << 2 | 3;
+                    break;
+                  }
+                ecode.push_back(code);
+              } else {
+                ecode.push_back(0);
+              }
             }
           }
+          gptr.push_back(int(rec.size()));
         }
-    }
-    std::vector<int> bptr(size_t(nt) * nl + 1, 0);
-    std::vector<double> bval;
-    for (size_t q = 0; q < terms.size(); q++) {
-      bptr[q + 1] = bptr[q] + int(terms[q].size());
-      bval.insert(bval.end(), terms[q].begin(), terms[q].end());
-    }
-    if ((rc = upv(seq_bptr, bptr, "seq boundary")) || (rc = upv(seq_bval, bval, "seq boundary")))
-      return rc;
-    std::vector<unsigned char> m(seq_mask_h.begin(), seq_mask_h.end());
-    if ((rc = upv(seq_mask, m, "seq mask"))) return rc;
-    if ((rc = upv(seq_phi, seq_phi_h, "seq phi")) || (rc = upv(seq_cp, seq_cp_h, "seq cp")) ||
-        (rc = upv(seq_cm, seq_cm_h, "seq cm")) || (rc = upv(seq_xold, seq_xold_h, "seq x_old")))
-      return rc;
-    seq_op_valid = true;
-    return PNP_OK;
-  }
-  pnp::SeqMesh seq_mesh() const {
-    pnp::SeqMesh M;
-    M.nv = mesh.nv;
-    M.nt = mesh.nt;
-    M.tri = seq_tri.p;
-    M.vptr = seq_vptr.p;
-    M.vinc = seq_vinc.p;
-    M.xy = seq_xy.p;
-    return M;
-  }
-  pnp::SeqOp seq_op() const {
-    pnp::SeqOp P;
-    P.kind = kind;
-    P.nf = nf;
-    P.cyl = params.cylindrical;
-    P.pi = params.pi;
-    P.l_b = params.l_b;
-    P.c0 = params.c0;
-    P.tau = params.tau;
-    P.dt = seq_dt;
-    P.z = seq_z;
-    P.phi = seq_phi_h.empty() ? nullptr : seq_phi.p;
-    P.cp = seq_cp_h.empty() ? nullptr : seq_cp.p;
-    P.cm = seq_cm_h.empty() ? nullptr : seq_cm.p;
-    P.x_old = seq_xold_h.empty() ? nullptr : seq_xold.p;
-    return P;
-  }
-  // r = R(x), both external layout on the device (GridOperator::residual + constraints)
-  int seq_residual(const double *x, double *r) {
-    int rc;
-    if ((rc = seq_prepare())) return rc;
-    const bool old = kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_DIFF_IMPLICIT_EULER;
-    hipError_t e = pnp::launch_seq_element(seq_mesh(), seq_op(), x, 0, seq_rl.p, seq_rlt.p,
-                                           seq_rlo.p, seq_jl.p, seq_jlt.p, seq_bptr.p, seq_bval.p,
-                                           stream);
-    if (e == hipSuccess)
-      e = pnp::launch_seq_residual_gather(seq_mesh(), nf, old ? 1 : 0, seq_rl.p, seq_rlt.p,
-                                          seq_rlo.p, seq_mask.p, r, stream);
-    return e == hipSuccess ? PNP_OK : hipfail(e, "seq residual");
-  }
-  // the CSR view = J(x) (GridOperator::jacobian + constrained rows to identity); fd: PDELab's
-  // NumericalJacobianVolume
-  int seq_jacobian(const double *x, bool fd) {
-    int rc;
-    if ((rc = seq_prepare()) || (rc = csr_structure())) return rc;
-    const bool onestep = kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_DIFF_IMPLICIT_EULER;
-    hipError_t e = pnp::launch_seq_element(seq_mesh(), seq_op(), x, fd ? 2 : 1, seq_rl.p,
-                                           seq_rlt.p, seq_rlo.p, seq_jl.p, seq_jlt.p, seq_bptr.p,
-                                           seq_bval.p, stream);
-    if (e == hipSuccess)
-      e = pnp::launch_seq_jacobian_gather(seq_mesh(), nf, seq_jl.p, onestep ? seq_jlt.p : nullptr,
-                                          csr_rowptr.p, csr_col.p,
-                                          seq_mask.p, csr_val.p, stream);
-    if (e != hipSuccess) return hipfail(e, "seq jacobian");
-    assembled = true;
-    csr_vals_valid = true;  // the CSR view holds this Jacobian; the k-form matrix does not
-    lu_valid = false;
-    split_of = 0;
-    amg_valid = false;
-    return PNP_OK;
-  }
-  double seq_dot(const double *a, const double *b, int &rc) {
-    rc = PNP_OK;
-    double h = 0;
-    hipError_t e = pnp::launch_seq_dot(nseq(), a, b, seq_dotv.p, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&h, seq_dotv.p, 8, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e != hipSuccess) rc = hipfail(e, "seq dot");
-    return h;
-  }
-  // v = M^{-1} d with v zero on entry (ISTL's preconditioners from y = 0)
-  int seq_prec(int prec, const double *d, double *v) {
-    const int n = nseq();
-    hipError_t e;
-    if (prec == PNP_PREC_NONE || prec == PNP_PREC_JACOBI) {
-      e = pnp::launch_seq_prec_diag(n, prec == PNP_PREC_JACOBI, d, csr_diag.p, csr_val.p, v, stream);
-    } else {  // SSOR_NATURAL: the natural-order sweep on the CSR view (internal positions)
-      e = pnp::launch_gather_ext(L.n_owned, nf, mesh.nv, d_l2g.p, d, nat_di.p, stream);
-      if (e == hipSuccess) e = nat_sweep(nat_di.p, nat_vi.p);
-      if (e == hipSuccess) e = pnp::launch_scatter_ext(L.n_owned, nf, mesh.nv, d_l2g.p, nat_vi.p, v, stream);
-    }
-    return e == hipSuccess ? PNP_OK : hipfail(e, "seq preconditioner");
-  }
-  // ISTL BiCGSTABSolver::apply in the oracle's statements (oracle/pnp_oracle.c orc_bicgstab):
-  // x (zero start) and b (overwritten by the residual), external layout on the device
-  int seq_bicgstab(int prec, double reduction, int maxit, double *x, double *b,
-                   pnp_solve_result &res) {
-    const double EPSILON = 1e-80;
-    const int n = nseq();
-    double *r = b, *p = sq(SQ_P), *v = sq(SQ_V), *t = sq(SQ_T), *y = sq(SQ_Y), *rt = sq(SQ_RT);
-    int rc = PNP_OK;
-    hipError_t e = hipSuccess;
-    auto ck = [&](hipError_t ee) {
-      if (e == hipSuccess) e = ee;
-    };
-    for (double *q : {p, v, t, y}) ck(hipMemsetAsync(q, 0, sizeof(double) * n, stream));
-    std::memset(&res, 0, sizeof res);
-    ck(pnp::launch_seq_spmv(n, csr_rowptr.p, csr_col.p, csr_val.p, x, t, stream));  // r = b - A x
-    ck(pnp::launch_seq_aymx(n, 1.0, r, t, stream));
-    ck(hipMemcpyAsync(rt, r, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
-    if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-    double norm = std::sqrt(seq_dot(r, r, rc)), norm_0 = norm;
-    if (rc) return rc;
-    double rho = 1, alpha = 1, omega = 1, rho_new = 0, beta, h;
-    res.defect0 = norm_0;
-    double it = 0;
-    if (norm < reduction * norm_0 || norm < 1e-30) {
-      res.converged = 1;
-      res.defect = norm;
-      return PNP_OK;
-    }
-    for (it = 0.5; it < maxit; it += .5) {
-      rho_new = seq_dot(rt, r, rc);
-      if (rc) return rc;
-      if (std::fabs(rho) <= EPSILON) { res.breakdown = 1; break; }
-      if (std::fabs(omega) <= EPSILON) { res.breakdown = 2; break; }
-      if (it < 1) {
-        ck(hipMemcpyAsync(p, r, sizeof(double) * n, hipMemcpyDeviceToDevice, stream));
-      } else {
-        beta = (rho_new / rho) * (alpha / omega);
-        ck(pnp::launch_seq_bicg_p(n, beta, omega, p, v, r, stream));
+        int rc2;
+        if ((rc2 = upv(W.cgptr, gptr, "natural SSOR chains")) ||
+            (rc2 = upv(W.crec, rec, "natural SSOR chains")) ||
+            (rc2 = upv(W.cecode, ecode, "natural SSOR chains")))
+          return rc2;
+        W.chain_groups = int(grows.size());
+        W.chain_wpad = wpad;
+        W.chain_ok = true;
       }
-      ck(hipMemsetAsync(y, 0, sizeof(double) * n, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      if ((rc = seq_prec(prec, p, y))) return rc;
-      ck(pnp::launch_seq_spmv(n, csr_rowptr.p, csr_col.p, csr_val.p, y, v, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      h = seq_dot(rt, v, rc);
-      if (rc) return rc;
-      if (std::fabs(h) < EPSILON) { res.breakdown = 3; break; }
-      alpha = rho_new / h;
-      ck(pnp::launch_seq_axpy2(n, alpha, x, y, r, v, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      norm = std::sqrt(seq_dot(r, r, rc));
-      if (rc) return rc;
-      if (norm < reduction * norm_0) { res.converged = 1; break; }
-      it += .5;
-      ck(hipMemsetAsync(y, 0, sizeof(double) * n, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      if ((rc = seq_prec(prec, r, y))) return rc;
-      ck(pnp::launch_seq_spmv(n, csr_rowptr.p, csr_col.p, csr_val.p, y, t, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      const double tr = seq_dot(t, r, rc);
-      if (rc) return rc;
-      const double tt = seq_dot(t, t, rc);
-      if (rc) return rc;
-      omega = tr / tt;
-      ck(pnp::launch_seq_axpy2(n, omega, x, y, r, t, stream));
-      if (e != hipSuccess) return hipfail(e, "seq bicgstab");
-      rho = rho_new;
-      norm = std::sqrt(seq_dot(r, r, rc));
-      if (rc) return rc;
-      if (norm < reduction * norm_0 || norm < 1e-30) { res.converged = 1; break; }
     }
-    if (it > maxit) it = maxit;
-    res.it_half = it;
-    res.iterations = int(std::ceil(it));
-    res.defect = norm;
-    res.reduction = norm / norm_0;
-    return PNP_OK;
-  }
-  // ISTL CGSolver::apply (orc_cg's statements)
-  int seq_cg(int prec, double reduction, int maxit, double *x, double *b, pnp_solve_result &res) {
-    const int n = nseq();
-    double *r = b, *p = sq(SQ_P), *q = sq(SQ_V);
-    int rc = PNP_OK;
-    hipError_t e = hipSuccess;
-    auto ck = [&](hipError_t ee) {
-      if (e == hipSuccess) e = ee;
-    };
-    ck(hipMemsetAsync(p, 0, sizeof(double) * n, stream));
-    ck(hipMemsetAsync(q, 0, sizeof(double) * n, stream));
-    std::memset(&res, 0, sizeof res);
-    ck(pnp::launch_seq_spmv(n, csr_rowptr.p, csr_col.p, csr_val.p, x, q, stream));
-    ck(pnp::launch_seq_aymx(n, 1.0, r, q, stream));
-    if (e != hipSuccess) return hipfail(e, "seq cg");
-    const double def0 = std::sqrt(seq_dot(r, r, rc));
-    if (rc) return rc;
-    double def = def0;
-    res.defect0 = def0;
-    int it = 0;
-    if (def0 < 1e-30) {
-      res.converged = 1;
-    } else {
-      if ((rc = seq_prec(prec, r, p))) return rc;
-      double rho = seq_dot(p, r, rc);
-      if (rc) return rc;
-      for (it = 1; it <= maxit; it++) {
-        ck(pnp::launch_seq_spmv(n, csr_rowptr.p, csr_col.p, csr_val.p, p, q, stream));
-        if (e != hipSuccess) return hipfail(e, "seq cg");
-        const double pq = seq_dot(p, q, rc);
-        if (rc) return rc;
-        const double lambda = rho / pq;
-        ck(pnp::launch_seq_axpy(n, lambda, x, p, stream));
-        ck(pnp::launch_seq_aymx(n, lambda, r, q, stream));
-        if (e != hipSuccess) return hipfail(e, "seq cg");
-        def = std::sqrt(seq_dot(r, r, rc));
-        if (rc) return rc;
-        if (def < reduction * def0 || def < 1e-30) {
-          res.converged = 1;
+    if (chain_rows > 0 && !W.chain_ok) {
+      // no chains (rows wider than the chain kernel takes): the tail is PNP_NAT_TAIL's again
+      // (default none), not the chain threshold's -- a one-workgroup tail of ~8K rows would run
+      // every narrow level on one CU
+      ltail = nlev;
+      while (tail_rows > 0 && ltail > 0 && lptr[ltail] - lptr[ltail - 1] <= tail_rows) ltail--;
+    }
+    for (int l = 0; l < nlev && nat_units_ok; l++) {
+      if (l == ltail) (fwd ? nat_tail_f : nat_tail_b) = int(nat_units.size());
+      const long long w = lwidth[l];
+      for (int t0 = lptr[l]; t0 < lptr[l + 1]; t0 += UR) {
+        const long long e0 = W.eoff[l] + (t0 - lptr[l]) / UR * w * UR;
+        if (w > 255 || W.eoff[l + 1] > INT32_MAX) {
+          nat_units_ok = false;
           break;
         }
-        ck(hipMemsetAsync(q, 0, sizeof(double) * n, stream));
-        if (e != hipSuccess) return hipfail(e, "seq cg");
-        if ((rc = seq_prec(prec, r, q))) return rc;
-        const double rho_new = seq_dot(q, r, rc);
-        if (rc) return rc;
-        const double beta = rho_new / rho;
-        ck(pnp::launch_seq_cg_p(n, beta, p, q, stream));
-        if (e != hipSuccess) return hipfail(e, "seq cg");
-        rho = rho_new;
+        const int rows = std::min(UR, lptr[l + 1] - t0);
+        nat_units.push_back(make_int4(t0, rows | int(w) << 8 | (fwd ? 0 : 1 << 16), UR, int(e0)));
+        nat_max_width = std::max(nat_max_width, int(w));
       }
-      if (it > maxit) it = maxit;
     }
-    res.it_half = it;
-    res.iterations = it;
-    res.defect = def;
-    res.reduction = def0 > 0 ? def / def0 : 0.0;
+    if (ltail >= nlev) (fwd ? nat_tail_f : nat_tail_b) = int(nat_units.size());
+    if (fwd) nat_units_f = int(nat_units.size());
+    int rc2;
+    if ((rc2 = upv(W.info, info, "natural SSOR rows"))) return rc2;
+    return upv(W.ecol, ecol, "natural SSOR columns");
+  };
+  nat_units.clear();
+  nat_units_ok = true;
+  nat_resident = -1;
+  nat_max_width = 0;
+  if ((rc = schedule(true, nat_f)) || (rc = schedule(false, nat_b))) return rc;
+  if (nat_units_ok && (rc = upv(d_nat_units, nat_units, "natural SSOR units"))) return rc;
+  const int ni = std::max(1, nf * (L.n_owned + L.n_ghost));  // internal layout
+  if ((e = nat_d.alloc(std::max(1, n))) != hipSuccess || (e = nat_v.alloc(std::max(1, n))) != hipSuccess ||
+      (e = nat_vf.alloc(std::max(1, n))) != hipSuccess || (e = nat_di.alloc(ni)) != hipSuccess ||
+      (e = nat_vi.alloc(ni)) != hipSuccess || (e = nat_abort.alloc(4)) != hipSuccess ||
+      (e = hipMemset(nat_abort.p, 0, 16)) != hipSuccess)
+    return hipfail(e, "natural SSOR vectors");
+  csr_nnz = nnz;
+  csr_pat = mask;
+  csr_nf = nf;
+  csr_vals_valid = false;
+  return PNP_OK;
+}
+
+// the CSR view's values from the current k-form matrix (once per assembly)
+int pnp_ctx::csr_values() {
+  int rc;
+  if ((rc = csr_structure())) return rc;
+  if (csr_vals_valid) return nat_probe_run();
+  if ((rc = ensure_values())) return rc;
+  hipError_t e = pnp::launch_csr_fill(dl, nf, pat, vals.p, csr_nnz, csr_src.p, csr_vidx.p,
+                                      csr_val.p, stream);
+  if (e != hipSuccess) return hipfail(e, "csr fill");
+  csr_vals_valid = true;
+  return nat_probe_run();
+}
+
+// one launch for both sweeps (ssor_natural.hip, launch_ssor_natural_flow) whenever this context
+// owns its GPU: one rank, or one rank of an RCCL communicator (one process per GPU, each rank
+// sweeping its owned rows -- block Jacobi across ranks, as ISTL's NOVLP SeqSSOR on the local
+// matrix).  The in-process local group keeps the level launches: its ranks share one device, and
+// the dataflow needs every workgroup of its grid resident.  PNP_NAT_FLOW=0 keeps the level
+// launches everywhere
+bool pnp_ctx::use_nat_flow() const {
+  static const bool env_on = [] {
+    const char *ev = std::getenv("PNP_NAT_FLOW");
+    return !(ev && std::atoi(ev) == 0);
+  }();
+  return nat_resident != 0 &&
+         (nat_flow_opt == 0   ? false
+          : nat_flow_opt == 1 ? nat_units_ok
+                              : env_on && !lg && !host_tr() && nat_units_ok);
+}
+
+int pnp_ctx::nat_probe_run() {
+  if (nat_resident >= 0 || !use_nat_flow()) return PNP_OK;
+  // test hook: PNP_NAT_PROBE_FAIL=1 takes the probe's "not resident" answer without running it
+  // (tests/test_gpu_ssor_natural.py: the level launches are then used, bitwise the same)
+  if (const char *ev = std::getenv("PNP_NAT_PROBE_FAIL"); ev && std::atoi(ev) == 1) {
+    nat_resident = 0;
     return PNP_OK;
   }
-  int seq_krylov(const pnp_solve_opts &o, double *x, double *b, pnp_solve_result &res) {
-    if (!assembled || !csr_vals_valid) return fail(PNP_E_STATE, "no Jacobian assembled");
-    if (o.prec != PNP_PREC_NONE && o.prec != PNP_PREC_JACOBI && o.prec != PNP_PREC_SSOR_NATURAL)
-      return fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: preconditioner must be NONE, JACOBI or SSOR_NATURAL");
-    double t0 = now_s();
-    int rc;
-    if (o.method == PNP_METHOD_CG)
-      rc = seq_cg(o.prec, o.reduction, o.maxit, x, b, res);
-    else if (o.method == PNP_METHOD_BICGSTAB)
-      rc = seq_bicgstab(o.prec, o.reduction, o.maxit, x, b, res);
-    else
-      return fail(PNP_E_ARG, "unknown solver method");
-    if (!rc && o.prec == PNP_PREC_SSOR_NATURAL) rc = nat_check();
-    res.elapsed = now_s() - t0;
-    return rc;
-  }
+  hipError_t e = nat_probe.p ? hipSuccess : nat_probe.alloc(2);
+  if (e != hipSuccess) return hipfail(e, "natural SSOR probe");
+  const int r = pnp::ssor_natural_flow_resident(nat_flow_view(), nat_probe.p, stream);
+  if (r < 0) return fail(PNP_E_HIP, "natural SSOR: co-residency probe failed");
+  nat_resident = r;
+  return PNP_OK;
+}
 
-  // the linear solver selected by o.method
-  int krylov(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res) {
-    int rc;
-    after_solve = true;
-    gm_history.clear();
-    if (o.method == PNP_METHOD_CG) {
-      amg_symmetric = true;
-      rc = cg(bdev, zout, o, res);
-    } else if (o.method == PNP_METHOD_BICGSTAB) {
-      amg_symmetric = false;
-      rc = bicgstab(bdev, zout, o, res, 0);
-    } else if (o.method == PNP_METHOD_GMRES || o.method == PNP_METHOD_FGMRES) {
-      amg_symmetric = false;
-      rc = gmres(bdev, zout, o, res, o.method == PNP_METHOD_FGMRES);
-    } else if (o.method == PNP_METHOD_IDR) {
-      amg_symmetric = false;
-      rc = idr(bdev, zout, o, res);
-    } else {
-      return fail(PNP_E_ARG, "unknown solver method");
-    }
-    amg_symmetric = true;
-    return rc;
+hipError_t pnp_ctx::nat_sweep(const double *d, double *vout) {
+  if (use_nat_flow()) {
+    nat_flow_n++;
+    return ssor_natural_flow(d, vout);
   }
-};
+  nat_level_n++;
+  return ssor_natural_levels(d, vout);
+}
+
+pnp::NatFlow pnp_ctx::nat_flow_view() const {
+  pnp::NatFlow F;
+  F.units = d_nat_units.p;
+  F.nunits = int(nat_units.size());
+  F.nunits_f = nat_units_f;
+  F.tail_f = nat_tail_f;
+  F.tail_b = nat_tail_b;
+  F.max_width = nat_max_width;
+  F.chain_f = nat_f.chains();
+  F.chain_b = nat_b.chains();
+  F.fwd = nat_f.view();
+  F.bwd = nat_b.view();
+  F.abort_word = nat_abort.p;
+  return F;
+}
+
+hipError_t pnp_ctx::ssor_natural_flow(const double *d, double *vout) {
+  const pnp::NatFlow F = nat_flow_view();
+  hipError_t e = pnp::launch_ssor_natural_flow(F, nf * mesh.nv, csr_val.p, d, nat_vf.p, nat_v.p,
+                                               stream);
+  // the result out of the external-layout vb (storing it at internal positions from the
+  // backward kernels as well cost more than this gather: +40 against 22 us, r5f)
+  if (e == hipSuccess)
+    e = pnp::launch_gather_ext(L.n_owned, nf, mesh.nv, d_l2g.p, nat_v.p, vout, stream);
+  return e;
+}
+
+// a dataflow sweep that timed out (never expected: every unit waits only on earlier units, all
+// resident) leaves NaN results and a sticky word; the solve reports it as an error
+int pnp_ctx::nat_check() {
+  if (!use_nat_flow() || !nat_abort.p) return PNP_OK;
+  unsigned w = 0;
+  hipError_t e = hipMemcpyAsync(&w, nat_abort.p, 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "natural SSOR status");
+  if (w) {
+    hipMemsetAsync(nat_abort.p, 0, 16, stream);
+    return fail(PNP_E_HIP, "natural SSOR: dataflow sweep timed out waiting for an operand");
+  }
+  return PNP_OK;
+}
+
+// ---- ILU(0) application as one dataflow launch (PNP_OPT_ILU_FLOW) -----------------------------
+// Units in the colour launches' order (forward colours c_first .. nc-2, the last colour, backward
+// colours nc-2 .. 0), one per 256-position block of the colour.  A unit's dependencies (all
+// earlier in the order): forward / last -- the forward units of the rows in its L staging list;
+// backward -- the backward (or last-colour) units of the rows in its U list, the forward units of
+// its own rows (their forward values are its input) and every forward unit whose L list holds one
+// of its rows (which must have read that row's forward value before it is overwritten).
+int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
+  D.built = true;
+  D.ok = false;
+  const int nc = int(L.color_ptr.size()) - 1;
+  const std::vector<int> &cp = L.color_ptr;
+  if (!dl.lsx_ptr || nc < 2 || h_posrowL.empty()) return PNP_OK;
+  std::vector<int> nb(nc), blk0(nc + 1, 0);
+  for (int c = 0; c < nc; c++) {
+    nb[c] = (cp[c + 1] - cp[c] + 255) / 256;
+    blk0[c + 1] = blk0[c] + nb[c];
+  }
+  std::vector<std::pair<int, int>> stages;  // {kind, colour}
+  for (int c = c_first; c < nc - 1; c++) stages.push_back({0, c});
+  stages.push_back({2, nc - 1});
+  for (int c = nc - 2; c >= 0; c--) stages.push_back({1, c});
+  if (int(stages.size()) > pnp::kIluFlowMaxStages) return PNP_OK;
+  pnp::IluFlow F;
+  F.nstages = int(stages.size());
+  int nu = 0;
+  for (int s = 0; s < F.nstages; s++) {
+    const int c = stages[s].second;
+    F.unit0[s] = nu;
+    F.kind[s] = stages[s].first;
+    F.r0[s] = cp[c];
+    F.r1[s] = cp[c + 1];
+    F.blk0[s] = blk0[c];
+    nu += nb[c];
+  }
+  F.unit0[F.nstages] = nu;
+  F.nunits = nu;
+  const int no = L.n_owned;
+  std::vector<int> fwdu(no, -1), bwdu(no, -1);
+  for (int s = 0; s < F.nstages; s++) {
+    const int c = stages[s].second, kind = stages[s].first;
+    for (int p = cp[c]; p < cp[c + 1]; p++) {
+      const int u = F.unit0[s] + (p - cp[c]) / 256;
+      if (kind != 1) fwdu[h_posrowL[p]] = u;
+      if (kind != 0) bwdu[h_posrowU[p]] = u;
+    }
+  }
+  // readers[r]: forward / last units whose L list holds row r (CSR)
+  std::vector<int> rptr(no + 1, 0), rdr;
+  auto lblock = [&](int s, int u) { return F.blk0[s] + (u - F.unit0[s]); };
+  for (int pass = 0; pass < 2; pass++) {
+    for (int s = 0; s < F.nstages; s++) {
+      if (F.kind[s] == 1) continue;
+      for (int u = F.unit0[s]; u < F.unit0[s + 1]; u++) {
+        const int b = lblock(s, u);
+        for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++) {
+          const int j = h_lsx_list[k];
+          if (pass == 0)
+            rptr[j + 1]++;
+          else
+            rdr[rptr[j]++] = u;
+        }
+      }
+    }
+    if (pass == 0) {
+      for (int r = 0; r < no; r++) rptr[r + 1] += rptr[r];
+      rdr.assign(rptr[no], 0);
+    } else {
+      for (int r = no; r > 0; r--) rptr[r] = rptr[r - 1];
+      rptr[0] = 0;
+    }
+  }
+  std::vector<int> dptr(nu + 1, 0), dlist, dep;
+  for (int s = 0; s < F.nstages; s++) {
+    const int c = stages[s].second;
+    for (int u = F.unit0[s]; u < F.unit0[s + 1]; u++) {
+      const int b = lblock(s, u);
+      dep.clear();
+      if (F.kind[s] != 1) {
+        for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++)
+          if (fwdu[h_lsx_list[k]] >= 0) dep.push_back(fwdu[h_lsx_list[k]]);
+      } else {
+        for (int k = h_usx_ptr[b]; k < h_usx_ptr[b + 1]; k++)
+          if (bwdu[h_usx_list[k]] >= 0) dep.push_back(bwdu[h_usx_list[k]]);
+        const int p0 = cp[c] + 256 * (u - F.unit0[s]), p1 = std::min(cp[c + 1], p0 + 256);
+        for (int p = p0; p < p1; p++) {
+          const int r = h_posrowU[p];
+          if (fwdu[r] >= 0) dep.push_back(fwdu[r]);
+          for (int k = rptr[r]; k < rptr[r + 1]; k++) dep.push_back(rdr[k]);
+        }
+      }
+      std::sort(dep.begin(), dep.end());
+      dep.erase(std::unique(dep.begin(), dep.end()), dep.end());
+      for (int w : dep)
+        if (w >= u) return fail(PNP_E_STATE, "ILU(0) dataflow: a unit depends on a later one");
+      dlist.insert(dlist.end(), dep.begin(), dep.end());
+      dptr[u + 1] = int(dlist.size());
+    }
+  }
+  if (dlist.empty()) dlist.push_back(0);
+  auto upv = [&](auto &buf, const auto &vec, const char *what) -> int {
+    hipError_t e2 = buf.alloc(vec.size());
+    if (e2 == hipSuccess)
+      e2 = hipMemcpy(buf.p, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice);
+    return e2 == hipSuccess ? PNP_OK : hipfail(e2, what);
+  };
+  int rc;
+  if ((rc = upv(D.dep_ptr, dptr, "ILU(0) dataflow deps")) ||
+      (rc = upv(D.dep_list, dlist, "ILU(0) dataflow deps")))
+    return rc;
+  hipError_t e = D.flags.alloc(size_t(nu + 1 + 3) & ~size_t(3));
+  if (e == hipSuccess && !ilu_flow_abort.p) {
+    e = ilu_flow_abort.alloc(4);
+    if (e == hipSuccess) e = hipMemset(ilu_flow_abort.p, 0, 16);
+  }
+  if (e != hipSuccess) return hipfail(e, "ILU(0) dataflow flags");
+  F.dep_ptr = D.dep_ptr.p;
+  F.dep_list = D.dep_list.p;
+  F.flags = D.flags.p;
+  F.abort_word = ilu_flow_abort.p;
+  D.F = F;
+  D.ok = true;
+  return PNP_OK;
+}
+
+// v = ILU(0)^-1 d over the owned rows, colours from c_first (launch_ilu0_apply's contract): one
+// dataflow launch when PNP_OPT_ILU_FLOW is on and d and v are distinct, else the colour launches
+int pnp_ctx::ilu_apply(const double *d, double *vout, int c_first, const char *what,
+                       hipEvent_t t0, hipEvent_t t1) {
+  // the resident-grid form needs the device to itself: not with in-process ranks sharing it
+  // (and one context per GPU at N > 1); PNP_ILU_FLOW_TICKET=1: the ticketed form (any residency)
+  // PNP_ILU_FLOW_MODE: IluFlow::persistent (0 ticket, 1 static resident grid, the default).
+  // A third form, a resident grid over 8 ticketed queues, hung in the bitwise tests (killed
+  // after 180 s of silence, gpurun_out r4i) and was removed
+  static const int mode = [] {
+    const char *ev = std::getenv("PNP_ILU_FLOW_MODE");
+    const int m = ev ? std::atoi(ev) : 1;
+    return (m >= 0 && m <= 1) ? m : 1;
+  }();
+  // PNP_OPT_ILU_FLOW = 2 selects the ticketed form (any residency, so also ranks sharing a GPU)
+  const int fmode = ilu_flow_opt == 2 ? 0 : mode;
+  if (ilu_flow_opt && d != vout && (c_first == 0 || c_first == 1) && (fmode == 0 || !dist)) {
+    IluFlowDev &D = ilu_flow[c_first];
+    int rc;
+    if (!D.built && (rc = ilu_flow_build(c_first, D))) return rc;
+    D.F.persistent = fmode;
+    if (D.ok) {
+      if (t0) hipEventRecord(t0, stream);
+      hipError_t e = pnp::launch_ilu0_flow(dl, D.F, nf, pat, lvals.p, uvals.p, d, vout, stream,
+                                           f32_now());
+      if (t1) hipEventRecord(t1, stream);
+      if (e != hipSuccess) return hipfail(e, what);
+      ilu_flow_used = true;
+      ilu_flow_n++;
+      return PNP_OK;
+    }
+  }
+  hipError_t e = pnp::launch_ilu0_apply(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, d,
+                                        vout, stream, c_first, nullptr, nullptr, f32_now(),
+                                        ilu_y32(), t0, t1);
+  return e == hipSuccess ? PNP_OK : hipfail(e, what);
+}
+
+// a dataflow application that timed out (never expected) leaves void results and a sticky word
+int pnp_ctx::ilu_flow_check() {
+  if (!ilu_flow_used || !ilu_flow_abort.p) return PNP_OK;
+  ilu_flow_used = false;
+  unsigned w = 0;
+  hipError_t e = hipMemcpyAsync(&w, ilu_flow_abort.p, 4, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "ILU(0) dataflow status");
+  if (w) {
+    hipMemsetAsync(ilu_flow_abort.p, 0, 16, stream);
+    return fail(PNP_E_HIP, "ILU(0) dataflow application timed out waiting for a unit");
+  }
+  return PNP_OK;
+}
+
+hipError_t pnp_ctx::ssor_natural_levels_fixed() {
+  auto issue = [&] {
+    hipError_t e0 = hipMemsetAsync(nat_v.p, 0, sizeof(double) * nat_v.n, stream);
+    return e0 != hipSuccess ? e0
+                            : pnp::launch_ssor_natural(nat_f.view(), nat_b.view(), csr_val.p,
+                                                       nat_d.p, nat_v.p, stream);
+  };
+  static const bool env_on = [] {
+    const char *ev = std::getenv("PNP_NAT_GRAPH");
+    return !(ev && std::atoi(ev) == 0);
+  }();
+  // not with more than one rank: in-process ranks share the device, and another rank's thread
+  // touching the legacy stream during a capture would invalidate it
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (!env_on || dist || nat_graph_failed || profiled() ||
+      hipStreamIsCapturing(stream, &cs) != hipSuccess ||
+      cs != hipStreamCaptureStatusNone)
+    return issue();
+  if (!nat_exec) {
+    hipError_t e = hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal);
+    if (e == hipSuccess) {
+      const hipError_t e1 = issue();
+      hipGraph_t g = nullptr;
+      const hipError_t e2 = hipStreamEndCapture(stream, &g);
+      e = e1 != hipSuccess ? e1 : e2;
+      if (e == hipSuccess) e = hipGraphInstantiate(&nat_exec, g, nullptr, nullptr, 0);
+      if (g) hipGraphDestroy(g);
+    }
+    if (e != hipSuccess || !nat_exec) {  // nothing of the capture ran: launch eagerly
+      (void)hipGetLastError();
+      nat_exec = nullptr;
+      nat_graph_failed = true;
+      return issue();
+    }
+  }
+  return hipGraphLaunch(nat_exec, stream);
+}
+
+// analytic (k-form) or forward-difference (expanded, kPat*FD) storage of the next Jacobian
+int pnp_ctx::set_fd(bool on) {
+  if (on == fd_mode) return PNP_OK;
+  graphs_clear();
+  int rc;
+  // P_k: the element kernel differentiates by itself; scalar blocks need no FD value layout
+  if (on && !fd_built && degree == 1 && (rc = fd_build())) return rc;
+  const int base = kind == PNP_OP_PNP ? pnp::kPatPnp
+                                      : (kind == PNP_OP_PNP_IMPLICIT_EULER ? pnp::kPatPnpIE
+                                                                          : pnp::kPatScalar);
+  pat = (on && nf == 3) ? (base | pnp::kPatFD) : base;
+  nks = pnp::nks_of(pat);
+  fd_mode = on;
+  assembled = false;
+  lu_valid = false;
+  split_of = 0;
+  amg_valid = false;
+  vals_const_valid = false;  // another value layout, zeroed below
+  if (on && degree == 1) {
+    // one-step operators keep two matrices per element (spatial, temporal: fd_jacobian.hip)
+    const size_t need = size_t(fd_ne) * 9 * nf * nf * 2;
+    if (fd_jel.n < need) {
+      hipError_t e = fd_jel.alloc(need);
+      if (e != hipSuccess) return hipfail(e, "fd element matrices");
+    }
+  }
+  // padding slots must read as zeros in the new value layout (the SpMV multiplies them)
+  hipError_t e = hipMemsetAsync(vals.p, 0, sizeof(double) * size_t(L.nslots) * nks, stream);
+  return e == hipSuccess ? PNP_OK : hipfail(e, "clear matrix");
+}
+
+// P_k element lists (once per context): the local elements (every element with an owned node,
+// ascending global id) and their local nodes (SoA); per owned row its incident elements in
+// ascending order, in SELL-chunk layout (PkDev), with the row's slot of every element node
+int pnp_ctx::pk_build() {
+  const pnp::Mesh &m = tmesh;
+  const int nl = pks.nl, nw = (nl + 3) / 4;
+  std::vector<int> en;
+  std::vector<int> elist;
+  for (int e = 0; e < m.nt; e++) {
+    const int *g = &pks.enode[size_t(e) * nl];
+    bool mine = false, local = true;
+    for (int a = 0; a < nl; a++) {
+      const int l = L.g2l[g[a]];
+      mine = mine || (l >= 0 && l < L.n_owned);
+      local = local && l >= 0;
+    }
+    if (!mine) continue;
+    if (!local) return fail(PNP_E_MESH, "P_k: element not local");
+    elist.push_back(e);
+  }
+  const int ne = int(elist.size());
+  if (ne >= (1 << 27)) return fail(PNP_E_MESH, "P_k: too many local elements");
+  en.resize(size_t(ne) * nl);
+  for (int e = 0; e < ne; e++)
+    for (int a = 0; a < nl; a++) en[size_t(a) * ne + e] = L.g2l[pks.enode[size_t(elist[e]) * nl + a]];
+  auto slot_of = [&](int row, int col) -> int {
+    const int ch = row / pnp::kRows, ln = row % pnp::kRows, len = pnp::meta_len(L.rowmeta[row]);
+    if (col == row) return 0;
+    for (int sl = 1; sl < len; sl++)
+      if (L.colidx[L.chunk_off[ch] + 64LL * sl + ln] == col) return sl;
+    return -1;
+  };
+  // incidences per owned row, ascending element order
+  std::vector<int> icnt(L.n_owned, 0);
+  for (int e = 0; e < ne; e++)
+    for (int a = 0; a < nl; a++) {
+      const int ra = en[size_t(a) * ne + e];
+      if (ra < L.n_owned) icnt[ra]++;
+    }
+  std::vector<int> ioff(L.nchunks + 1, 0);
+  for (int c = 0; c < L.nchunks; c++) {
+    int mx = 0;
+    for (int ln = 0; ln < pnp::kRows && c * pnp::kRows + ln < L.n_owned; ln++)
+      mx = std::max(mx, icnt[c * pnp::kRows + ln]);
+    ioff[c + 1] = ioff[c] + pnp::kRows * mx;
+  }
+  std::vector<int> inc(std::max(1, ioff[L.nchunks]), 0), fill(L.n_owned, 0);
+  std::vector<uint32_t> islot(size_t(std::max(1, ioff[L.nchunks])) * nw, 0);
+  for (int e = 0; e < ne; e++)
+    for (int a = 0; a < nl; a++) {
+      const int ra = en[size_t(a) * ne + e];
+      if (ra >= L.n_owned) continue;
+      const int c = ra / pnp::kRows, ln = ra % pnp::kRows;
+      const size_t p = size_t(ioff[c]) + size_t(pnp::kRows) * fill[ra]++ + ln;
+      inc[p] = e << 4 | a;
+      for (int b = 0; b < nl; b++) {
+        const int sl = slot_of(ra, en[size_t(b) * ne + e]);
+        if (sl < 0) return fail(PNP_E_MESH, "P_k: element pair outside the pattern");
+        islot[p * nw + (b >> 2)] |= uint32_t(sl) << (8 * (b & 3));
+      }
+    }
+  int rc;
+  if ((rc = upv(pk_enode, en, "P_k elements")) || (rc = upv(pk_ioff, ioff, "P_k ioff")) ||
+      (rc = upv(pk_icnt, icnt, "P_k icnt")) || (rc = upv(pk_inc, inc, "P_k incidences")) ||
+      (rc = upv(pk_islot, islot, "P_k slots")))
+    return rc;
+  hipError_t e = pk_eres.alloc(std::max<size_t>(1, size_t(ne) * nl));
+  if (e != hipSuccess) return hipfail(e, "P_k element residual scratch");
+  e = pk_ejac.alloc(std::max<size_t>(1, size_t(ne) * nl * ((nl + 2) & ~1)));
+  if (e != hipSuccess) return hipfail(e, "P_k element matrix scratch");
+  e = pnp::pk_upload_tables(pks.k, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) return hipfail(e, "P_k tables");
+  pkd.k = pks.k;
+  pkd.nl = nl;
+  pkd.ne = ne;
+  pkd.enode = pk_enode.p;
+  pkd.ioff = pk_ioff.p;
+  pkd.icnt = pk_icnt.p;
+  pkd.inc = pk_inc.p;
+  pkd.islot = pk_islot.p;
+  pkd.eres = pk_eres.p;
+  pkd.ejac = pk_ejac.p;
+  // the Jacobian gather pass accumulates a row's slots in LDS, sized for the longest row: the
+  // vertex rows (up to 55 slots at P3) would hold every workgroup to one per CU.  When the
+  // longest row needs more than 64 KB per workgroup, blocks whose rows are all at most the
+  // median block length (the edge and interior node rows) run in a launch of their own with an
+  // LDS accumulator of that length: P3 438 -> 395 us; at P2 (one launch at 3 workgroups per CU)
+  // the second launch costs more than it gains, 135 -> 145 us (profiles/r02/ab_pk_split).
+  // PNP_PK_SPLIT=0: always one launch, 1: split whenever the median is at most half the longest
+  {
+    const char *ev = getenv("PNP_PK_SPLIT");
+    const int nblk = (L.n_owned + 255) / 256;
+    std::vector<int> order(nblk), blen(nblk, 0);
+    for (int b = 0; b < nblk; b++) order[b] = b;
+    if (dl.blkmap && nblk > 0) {
+      e = hipMemcpy(order.data(), dl.blkmap, sizeof(int) * nblk, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return hipfail(e, "blkmap");
+    }
+    for (int r = 0; r < L.n_owned; r++)
+      blen[r / 256] = std::max(blen[r / 256], pnp::meta_len(L.rowmeta[r]));
+    std::vector<int> srt(blen);
+    std::nth_element(srt.begin(), srt.begin() + nblk / 2, srt.end());
+    const int T = nblk > 0 ? srt[nblk / 2] : 0;
+    const int mx = nblk > 0 ? *std::max_element(blen.begin(), blen.end()) : 0;
+    const bool want = ev ? ev[0] == '1' : size_t(mx) * 256 * sizeof(double) > 64 * 1024;
+    if (want && nblk > 0 && 2 * T <= mx) {
+      std::vector<int> sh, lo;
+      for (int b : order) (blen[b] <= T ? sh : lo).push_back(b);
+      if ((rc = upv(pk_blk_short, sh, "P_k short blocks")) ||
+          (rc = upv(pk_blk_long, lo, "P_k long blocks")))
+        return rc;
+      pkd.blk_short = pk_blk_short.p;
+      pkd.blk_long = pk_blk_long.p;
+      pkd.n_short = int(sh.size());
+      pkd.n_long = int(lo.size());
+      pkd.short_len = T;
+    }
+  }
+  // ion-flux segments handled by this rank: those whose element is local and whose lower
+  // global vertex is owned here, {local element, face, group}, in global segment order
+  std::vector<int> eloc(m.nt, -1);
+  for (int e2 = 0; e2 < ne; e2++) eloc[elist[e2]] = e2;
+  std::vector<int4> segs;
+  fseg_group.clear();
+  for (int sg = 0; sg < m.nb; sg++) {
+    const int a = m.bseg[2 * size_t(sg)], b = m.bseg[2 * size_t(sg) + 1];
+    const int lo = L.g2l[std::min(a, b)];
+    if (lo < 0 || lo >= L.n_owned) continue;
+    const int bf = pks.bface[sg];
+    if (bf < 0 || eloc[bf / 3] < 0) return fail(PNP_E_MESH, "ion flux: the element of a boundary segment is not local");
+    segs.push_back(make_int4(eloc[bf / 3], bf % 3, m.bgroup[sg], 0));
+    fseg_group.push_back(m.bgroup[sg]);
+  }
+  if ((rc = upv(d_fseg, segs, "P_k flux segments"))) return rc;
+  e = fluxout.alloc(2 * segs.size() + 2);
+  if (e != hipSuccess) return hipfail(e, "flux out");
+  return PNP_OK;
+}
+
+// local elements (ascending global id, vertices in mesh order) and, per owned row and slot, the
+// element entries summed into that block, in ascending element order
+int pnp_ctx::fd_build() {
+  const pnp::Mesh &m = mesh;
+  std::vector<int> et;
+  for (int e = 0; e < m.nt; e++) {
+    const int *t = &m.tri[3 * size_t(e)];
+    const int l0 = L.g2l[t[0]], l1 = L.g2l[t[1]], l2 = L.g2l[t[2]];
+    const bool mine = (l0 >= 0 && l0 < L.n_owned) || (l1 >= 0 && l1 < L.n_owned) ||
+                      (l2 >= 0 && l2 < L.n_owned);
+    if (!mine) continue;
+    if (l0 < 0 || l1 < 0 || l2 < 0) return fail(PNP_E_MESH, "FD Jacobian: element not local");
+    et.push_back(l0);
+    et.push_back(l1);
+    et.push_back(l2);
+  }
+  const int ne = int(et.size() / 3);
+  auto pos_of = [&](int row, int col) -> long long {
+    const int ch = row / pnp::kRows, ln = row % pnp::kRows, len = pnp::meta_len(L.rowmeta[row]);
+    if (col == row) return L.chunk_off[ch] + ln;
+    for (int sl = 1; sl < len; sl++) {
+      const long long p = L.chunk_off[ch] + 64LL * sl + ln;
+      if (L.colidx[p] == col) return p;
+    }
+    return -1;
+  };
+  std::vector<int> cnt(size_t(L.nslots) + 1, 0);
+  for (int e = 0; e < ne; e++)
+    for (int a = 0; a < 3; a++) {
+      const int va = et[3 * size_t(e) + a];
+      if (va >= L.n_owned) continue;
+      for (int b = 0; b < 3; b++) {
+        const long long p = pos_of(va, et[3 * size_t(e) + b]);
+        if (p < 0) return fail(PNP_E_MESH, "FD Jacobian: element pair outside the pattern");
+        cnt[p]++;
+      }
+    }
+  // per row: for each slot, the count then its codes
+  std::vector<long long> rptr(L.n_owned + 1, 0);
+  for (int i = 0; i < L.n_owned; i++) {
+    const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
+    long long n = 0;
+    for (int sl = 0; sl < len; sl++) n += 1 + cnt[L.chunk_off[ch] + 64LL * sl + ln];
+    rptr[i + 1] = rptr[i] + n;
+  }
+  std::vector<long long> at((size_t)L.nslots, -1LL);  // next free code position of each block
+  std::vector<int> data((size_t)rptr[L.n_owned]);
+  for (int i = 0; i < L.n_owned; i++) {
+    const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
+    long long q = rptr[i];
+    for (int sl = 0; sl < len; sl++) {
+      const long long p = L.chunk_off[ch] + 64LL * sl + ln;
+      data[q] = cnt[p];
+      at[p] = q + 1;
+      q += 1 + cnt[p];
+    }
+  }
+  for (int e = 0; e < ne; e++)
+    for (int a = 0; a < 3; a++) {
+      const int va = et[3 * size_t(e) + a];
+      if (va >= L.n_owned) continue;
+      for (int b = 0; b < 3; b++) {
+        const long long p = pos_of(va, et[3 * size_t(e) + b]);
+        data[at[p]++] = e * 9 + a * 3 + b;
+      }
+    }
+  int rc;
+  if ((rc = upv(fd_etri, et, "fd elements")) || (rc = upv(fd_rptr, rptr, "fd rptr")) ||
+      (rc = upv(fd_cdata, data, "fd contributions")))
+    return rc;
+  fd_ne = ne;
+  fd_built = true;
+  return PNP_OK;
+}
+
+// ILU(0) factors of the current matrix (once per assembly).  Default: the fused factorisation
+// (expand and split folded in, neighbour-row work hoisted; PNP_OPT_ILU_FUSED_FACTOR = 0 runs the
+// three-pass path, the same bits)
+int pnp_ctx::ilu_factor() {
+  if (lu_valid) return PNP_OK;
+  if (int rc = ensure_values()) return rc;
+  hipEvent_t t0 = tb(T_FACT);
+  hipError_t e;
+  if (ilu_fused) {
+    e = pnp::launch_ilu0_factor_fused(dl, L.color_ptr.data(), nf, pat, vals.p, d_rowoff.p,
+                                      d_rowcol.p, lu.p, lvals.p, uvals.p, ilu_fac(), stream);
+  } else {
+    e = pnp::launch_expand(dl, nf, pat, vals.p, lu.p, stream);
+    if (e == hipSuccess)
+      e = pnp::launch_ilu0_factor(dl, L.color_ptr.data(), nf, pat, lu.p, stream);
+  }
+  if (e != hipSuccess) return hipfail(e, "ilu0 factorisation");
+  te(T_FACT, t0);
+  lu_valid = true;
+  split_of = ilu_fused ? 2 : 0;
+  return PNP_OK;
+}
+
+// bring the split storage up to date with the matrix (which = 1) or the factors (which = 2)
+int pnp_ctx::split(int which) {
+  if (split_of == which) return PNP_OK;
+  if (which == 2 && ilu_fused) {  // the fused factorisation keeps no SELL copy: redo it
+    lu_valid = false;
+    return ilu_factor();
+  }
+  if (which == 1)
+    if (int rc = ensure_values()) return rc;
+  hipEvent_t t0 = tb(T_FACT);
+  hipError_t e = pnp::launch_split(dl, nf, pat, which == 1 ? 1 : 0, which == 2 ? lu.p : vals.p,
+                                   d_lsrc.p, (long long)d_lsrc.n, d_usrc.p, (long long)d_usrc.n,
+                                   lvals.p, uvals.p, stream, which == 2 ? ilu_fac() : 0);
+  if (e != hipSuccess) return hipfail(e, "split");
+  te(T_FACT, t0);
+  split_of = which;
+  return PNP_OK;
+}
+
+// hierarchy patterns (once), value/vector buffers (per field count), coarse values (per
+// assembly): Galerkin sums, block-diagonal inverses, the coarsest dense inverse
+int pnp_ctx::amg_setup() {
+  int rc;
+  if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
+  // the Galerkin products and the V-cycle's level-0 residuals read the SELL values
+  if ((rc = ensure_values())) return rc;
+  if (!amg_built) {
+    amg_d.clear();
+    if (!pnp::amg_build(L, amg_opts.coarse_target, amg_opts.max_levels, amg_h, err))
+      return PNP_E_STATE;
+    for (const auto &H : amg_h) {
+      auto D = std::make_unique<AmgDev>();
+      D->nb = H.nb;
+      if ((rc = upv(D->rp, H.rp, "amg rp")) || (rc = upv(D->col, H.col, "amg col")) ||
+          (rc = upv(D->dpos, H.dpos, "amg dpos")) || (rc = upv(D->mptr, H.mptr, "amg mptr")) ||
+          (rc = upv(D->mem, H.mem, "amg mem")) || (rc = upv(D->agg, H.agg, "amg agg")) ||
+          (rc = upv(D->csrc, H.csrc, "amg csrc")) || (rc = upv(D->cptr, H.cptr, "amg cptr")))
+        return rc;
+      amg_d.push_back(std::move(D));
+    }
+    amg_built = true;
+    amg_nf = 0;
+  }
+  if (amg_d.empty()) return fail(PNP_E_STATE, "AMG: no owned rows");
+  const int K = int(amg_d.size());
+  if (amg_d[K - 1]->nb * nf > pnp::kAmgMaxDense)
+    return fail(PNP_E_STATE, "AMG: coarsest level too large for the dense solve");
+  if (amg_nf != nf) {
+    const size_t nb2 = size_t(nf) * nf;
+    for (auto &D : amg_d) {
+      hipError_t e;
+      if ((amg_f32() && D.get() != amg_d.back().get() &&
+           (e = D->vf.alloc(std::max<size_t>(1, D->col.n) * nb2)) != hipSuccess) ||
+          (e = D->v.alloc(std::max<size_t>(1, D->col.n) * nb2)) != hipSuccess ||
+          (e = D->dinv.alloc(size_t(D->nb) * nb2)) != hipSuccess ||
+          (e = D->b.alloc(size_t(D->nb) * nf)) != hipSuccess ||
+          (e = D->x.alloc(size_t(D->nb) * nf)) != hipSuccess ||
+          (e = D->x2.alloc(size_t(D->nb) * nf)) != hipSuccess)
+        return hipfail(e, "amg level buffers");
+    }
+    const size_t nc = size_t(amg_d[K - 1]->nb) * nf, nl = size_t(L.n_owned + L.n_ghost) * nf;
+    hipError_t e;
+    amg_ld = int((nc + 3) & ~size_t(3));
+    if ((amg_f32() && (e = amg_ainv_f.alloc(nc * size_t(amg_ld))) != hipSuccess) ||
+        (e = amg_ainv.alloc(nc * nc)) != hipSuccess || (e = amg_ipiv.alloc(nc)) != hipSuccess ||
+        (e = amg_info.alloc(1)) != hipSuccess ||
+        (e = amg_x0.alloc(nl)) != hipSuccess || (e = amg_t.alloc(nl)) != hipSuccess ||
+        (e = amg_y.alloc(nl)) != hipSuccess || (e = amg_r.alloc(nl)) != hipSuccess ||
+        (e = amg_z.alloc(nl)) != hipSuccess)
+      return hipfail(e, "amg vectors");
+    amg_nf = nf;
+    amg_valid = false;
+  }
+  // (a Jacobi smoother's prerequisite is a no-op here: ensure_values() above left vals current)
+  if ((rc = prec_prepare(amg_opts.smoother))) return rc;
+  if (amg_valid) return PNP_OK;
+  hipEvent_t t0 = tb(T_FACT);
+  double ts = now_s();
+  hipError_t e = pnp::launch_amg_galerkin0(dl, nf, pat, vals.p, (long long)amg_h[0].col.size(),
+                                           amg_d[0]->cptr.p, amg_d[0]->csrc.p, amg_d[0]->v.p,
+                                           stream);
+  for (int k = 1; k < K && e == hipSuccess; k++)
+    e = pnp::launch_amg_galerkin(nf, (long long)amg_h[k].col.size(), amg_d[k]->cptr.p,
+                                 amg_d[k]->csrc.p, amg_d[k - 1]->v.p, amg_d[k]->v.p, stream);
+  for (int k = 0; k + 1 < K && e == hipSuccess; k++)
+    e = pnp::launch_amg_dinv(nf, amg_d[k]->nb, amg_d[k]->dpos.p, amg_d[k]->v.p,
+                             amg_d[k]->dinv.p, stream);
+  for (int k = 0; k + 1 < K && e == hipSuccess; k++)
+    if (amg_d[k]->vf.p)
+      e = pnp::launch_amg_to_f32((long long)amg_d[k]->col.n * nf * nf, amg_d[k]->v.p,
+                                 amg_d[k]->vf.p, stream);
+  if (e == hipSuccess)
+    e = pnp::launch_amg_coarse_dense(nf, amg_d[K - 1]->nb, amg_d[K - 1]->rp.p,
+                                     amg_d[K - 1]->col.p, amg_d[K - 1]->v.p, amg_ainv.p, stream);
+  if (e != hipSuccess) return hipfail(e, "amg setup");
+  {  // coarsest inverse in place: LU with partial pivoting, then the inverse -- of A^T column-
+     // major, which leaves A^-1 row-major for k_coarse_apply
+    if (!blas) {
+      if (rocblas_create_handle(&blas) != rocblas_status_success)
+        return fail(PNP_E_HIP, "rocblas_create_handle failed");
+    }
+    if (rocblas_set_stream(blas, stream) != rocblas_status_success)
+      return fail(PNP_E_HIP, "rocblas_set_stream failed");
+    const int nc = amg_d[K - 1]->nb * nf;
+    if (rocsolver_dgetrf(blas, nc, nc, amg_ainv.p, nc, amg_ipiv.p, amg_info.p) !=
+            rocblas_status_success ||
+        rocsolver_dgetri(blas, nc, amg_ainv.p, nc, amg_ipiv.p, amg_info.p) !=
+            rocblas_status_success)
+      return fail(PNP_E_HIP, "rocsolver getrf/getri of the AMG coarsest level failed");
+    int info = 0;
+    e = hipMemcpyAsync(&info, amg_info.p, sizeof info, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "amg setup");
+    if (info != 0)
+      return fail(PNP_E_STATE, "AMG: coarsest matrix singular (getrf info " +
+                                   std::to_string(info) + ")");
+    if (amg_ainv_f.p &&
+        (e = pnp::launch_amg_inverse_to_f32(nc, amg_ld, amg_ainv.p, amg_ainv_f.p, stream)) !=
+            hipSuccess)
+      return hipfail(e, "amg setup");
+  }
+  te(T_FACT, t0);
+  amg_setup_ms = (now_s() - ts) * 1e3;  // host-side issue time (device time: T_FACT timers)
+  amg_valid = true;
+  return PNP_OK;
+}
+
+// one V-cycle: vout = B d (owned rows); see amg.hip for the kernels
+int pnp_ctx::amg_apply(const double *d, double *vout) {
+  const int K = int(amg_d.size()), sm = amg_opts.smoother, n = L.n_owned;
+  const double om = amg_opts.omega;
+  const long long nn = nown();
+  int rc, nsp = 0;
+  hipError_t e;
+  // level 0 pre-smoothing from zero, residual (SpMV residual mode), restriction (+ level-1
+  // pre-smoothing); without level-0 pre-smoothing x0 = 0 and the restriction takes d itself
+  // amg_opts.level0_presmooth: 1 always, 0 never, -1 (auto) only when the V-cycle must stay
+  // symmetric (CG, or a bare pnp_prec_apply); BiCGSTAB takes the post-smoothing-only cycle
+  const bool pre0 = amg_opts.level0_presmooth > 0 ||
+                    (amg_opts.level0_presmooth < 0 && amg_symmetric);
+  if (pre0) {
+    if ((rc = smoother(sm, d, amg_x0.p))) return rc;
+    e = pnp::launch_spmv(dl, nf, pat, vals.p, amg_x0.p, amg_t.p, 3, d, partials.p, &nsp,
+                         stream);
+  } else {
+    e = hipSuccess;  // x0 = 0: the restriction takes d, the prolongation no x0
+  }
+  if (e == hipSuccess)
+    e = pnp::launch_amg_restrict(nf, amg_d[0]->nb, amg_d[0]->mptr.p, amg_d[0]->mem.p,
+                                 pre0 ? amg_t.p : d, nullptr, amg_d[0]->b.p, amg_d[0]->dinv.p,
+                                 om, K > 1 ? amg_d[0]->x.p : nullptr, stream);
+  for (int k = 0; k + 1 < K && e == hipSuccess; k++) {
+    AmgDev &C = *amg_d[k], &N = *amg_d[k + 1];
+    for (int sw = 1; sw < amg_sweeps(k) && e == hipSuccess; sw++) {  // more pre-smoothing
+      e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, nullptr, C.x.p,
+                               nullptr, C.b.p, C.dinv.p, om, C.x2.p, stream);
+      std::swap(C.x.p, C.x2.p);
+    }
+    // residual of level k+1 into its x2 (free until its post-smoothing), then restriction
+    if (e == hipSuccess)
+      e = pnp::launch_amg_resid(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, C.x.p, C.b.p,
+                                C.x2.p, stream);
+    if (e == hipSuccess)
+      e = pnp::launch_amg_restrict(nf, N.nb, N.mptr.p, N.mem.p, C.x2.p, nullptr, N.b.p,
+                                   N.dinv.p, om, k + 2 < K ? N.x.p : nullptr, stream);
+  }
+  if (e == hipSuccess)
+    e = amg_ainv_f.p
+            ? pnp::launch_amg_coarse_apply_f32(amg_d[K - 1]->nb * nf, amg_ld, amg_ainv_f.p,
+                                               amg_d[K - 1]->b.p, amg_d[K - 1]->x.p, stream)
+            : pnp::launch_amg_coarse_apply(amg_d[K - 1]->nb * nf, amg_ainv.p, amg_d[K - 1]->b.p,
+                                     amg_d[K - 1]->x.p, stream);
+  const double *res = amg_d[K - 1]->x.p;  // the solution of the level just finished
+  for (int k = K - 2; k >= 0 && e == hipSuccess; k--) {
+    AmgDev &C = *amg_d[k];
+    e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, amg_d[k + 1]->agg.p,
+                             C.x.p, res, C.b.p, C.dinv.p, om, C.x2.p, stream);
+    res = C.x2.p;
+    for (int sw = 1; sw < amg_sweeps(k) && e == hipSuccess; sw++) {  // more post-smoothing
+      double *out = res == C.x2.p ? C.x.p : C.x2.p;
+      e = pnp::launch_amg_post(nf, C.nb, C.rp.p, C.col.p, C.v.p, C.vf.p, nullptr, res,
+                               nullptr, C.b.p, C.dinv.p, om, out, stream);
+      res = out;
+    }
+  }
+  // level 0: prolongation, post-smoothing x += M^{-1} (d - A x)
+  if (e == hipSuccess)
+    e = pnp::launch_amg_prolong0(nf, n, amg_d[0]->agg.p, pre0 ? amg_x0.p : nullptr, res,
+                                 amg_y.p, stream);
+  if (e == hipSuccess)
+    e = pnp::launch_spmv(dl, nf, pat, vals.p, amg_y.p, amg_r.p, 3, d, partials.p, &nsp, stream);
+  if (e != hipSuccess) return hipfail(e, "amg v-cycle");
+  if (sm == PNP_PREC_ILU0) {  // vout = y + M^-1 r, written by the backward sweep
+    e = pnp::launch_ilu0_apply(dl, L.color_ptr.data(), nf, pat, lvals.p, uvals.p, amg_r.p,
+                               amg_z.p, stream, 0, amg_y.p, vout, f32_now(), ilu_y32());
+    return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
+  }
+  if ((rc = smoother(sm, amg_r.p, amg_z.p))) return rc;
+  e = pnp::launch_axpby(nn, 1.0, amg_y.p, 1.0, amg_z.p, vout, stream);
+  return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
+}
+
+int pnp_ctx::seq_build() {
+  if (seq_built) return PNP_OK;
+  const int nv = mesh.nv, nt = mesh.nt;
+  std::vector<int> vptr(nv + 1, 0), vinc(size_t(3) * nt);
+  for (int e = 0; e < nt; e++)
+    for (int a = 0; a < 3; a++) vptr[mesh.tri[3 * e + a] + 1]++;
+  for (int v = 0; v < nv; v++) vptr[v + 1] += vptr[v];
+  std::vector<int> fill(vptr.begin(), vptr.end() - 1);
+  for (int e = 0; e < nt; e++)  // ascending element index per vertex
+    for (int a = 0; a < 3; a++) vinc[fill[mesh.tri[3 * e + a]]++] = e << 2 | a;
+  int rc;
+  if ((rc = upv(seq_tri, mesh.tri, "seq tri")) || (rc = upv(seq_xy, mesh.xy, "seq xy")) ||
+      (rc = upv(seq_vptr, vptr, "seq vptr")) || (rc = upv(seq_vinc, vinc, "seq vinc")))
+    return rc;
+  hipError_t e;
+  if ((e = seq_vec.alloc(size_t(SQ_N) * 3 * nv)) != hipSuccess ||
+      (e = seq_dotv.alloc(2)) != hipSuccess || (e = seq_rl.alloc(size_t(9) * nt)) != hipSuccess ||
+      (e = seq_rlo.alloc(size_t(9) * nt)) != hipSuccess ||
+      (e = seq_rlt.alloc(size_t(9) * nt)) != hipSuccess ||
+      (e = seq_jl.alloc(size_t(81) * nt)) != hipSuccess ||
+      (e = seq_jlt.alloc(size_t(81) * nt)) != hipSuccess)
+    return hipfail(e, "seq buffers");
+  seq_built = true;
+  return PNP_OK;
+}
+
+// per operator: constrained rows, alpha_boundary's terms per (element, local index) in the order
+// PDELab adds them into the element's local vector (the oracle's boundary_face statements: the
+// element's faces in DUNE's order (0,1), (0,2), (1,2), each a boundary intersection when its edge
+// is a boundary segment, run from its lower to its higher local vertex; 2-point Gauss; fields in
+// order; every basis function of the element at the face point; rl += scale * (j * phi * factor)),
+// frozen fields
+int pnp_ctx::seq_prepare() {
+  int rc;
+  if ((rc = seq_build())) return rc;
+  if (seq_op_valid) return PNP_OK;
+  if (seq_cextra) return fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: pnp_op_args.c_extra is not supported");
+  const int nt = mesh.nt, nl = 3 * nf;
+  std::vector<std::vector<double>> terms(size_t(nt) * nl);
+  const bool bnd = kind == PNP_OP_PNP || kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_PB ||
+                   kind == PNP_OP_POISSON;
+  if (bnd) {
+    std::unordered_map<long long, int> seg;  // edge -> its (first) boundary segment
+    auto key = [](int a, int b) { return (long long)std::min(a, b) << 32 | unsigned(std::max(a, b)); };
+    for (int b = 0; b < mesh.nb; b++) seg.emplace(key(mesh.bseg[2 * b], mesh.bseg[2 * b + 1]), b);
+    static const int kFaceV[3][2] = {{0, 1}, {0, 2}, {1, 2}};
+    static const double corner[3][2] = {{0.0, 0.0}, {1.0, 0.0}, {0.0, 1.0}};
+    const double PI = params.pi;
+    const double scale = kind == PNP_OP_PNP_IMPLICIT_EULER ? seq_dt : 1.0;
+    const double gt[2] = {0.5 - 0.5 / std::sqrt(3.0), 0.5 + 0.5 / std::sqrt(3.0)};
+    for (int e = 0; e < nt && !seg.empty(); e++)
+      for (int k = 0; k < 3; k++) {
+        const int ia = kFaceV[k][0], ib = kFaceV[k][1];
+        const int va = mesh.tri[3 * e + ia], vb = mesh.tri[3 * e + ib];
+        const auto it = seg.find(key(va, vb));
+        if (it == seg.end()) continue;
+        const pnp::Surface &S = params.surf[mesh.bgroup[it->second]];
+        const double dx = mesh.xy[2 * vb] - mesh.xy[2 * va],
+                     dy = mesh.xy[2 * vb + 1] - mesh.xy[2 * va + 1];
+        const double len = std::sqrt(dx * dx + dy * dy);
+        for (int q = 0; q < 2; q++) {
+          double factor = 0.5 * len;
+          const double y = mesh.xy[2 * va + 1] + gt[q] * dy;
+          if (params.cylindrical) factor *= y * 2 * PI;
+          const double lx = corner[ia][0] + (corner[ib][0] - corner[ia][0]) * gt[q];
+          const double ly = corner[ia][1] + (corner[ib][1] - corner[ia][1]) * gt[q];
+          const double phi[3] = {1.0 - lx - ly, lx, ly};
+          for (int f = 0; f < nf; f++) {
+            if (S.btype(f) == 0) continue;  // isDirichlet
+            const double j = S.flux(f);
+            for (int i = 0; i < 3; i++)
+              terms[size_t(e) * nl + 3 * f + i].push_back(scale * (j * phi[i] * factor));
+          }
+        }
+      }
+  }
+  std::vector<int> bptr(size_t(nt) * nl + 1, 0);
+  std::vector<double> bval;
+  for (size_t q = 0; q < terms.size(); q++) {
+    bptr[q + 1] = bptr[q] + int(terms[q].size());
+    bval.insert(bval.end(), terms[q].begin(), terms[q].end());
+  }
+  if ((rc = upv(seq_bptr, bptr, "seq boundary")) || (rc = upv(seq_bval, bval, "seq boundary")))
+    return rc;
+  std::vector<unsigned char> m(seq_mask_h.begin(), seq_mask_h.end());
+  if ((rc = upv(seq_mask, m, "seq mask"))) return rc;
+  if ((rc = upv(seq_phi, seq_phi_h, "seq phi")) || (rc = upv(seq_cp, seq_cp_h, "seq cp")) ||
+      (rc = upv(seq_cm, seq_cm_h, "seq cm")) || (rc = upv(seq_xold, seq_xold_h, "seq x_old")))
+    return rc;
+  seq_op_valid = true;
+  return PNP_OK;
+}
+
+pnp::SeqMesh pnp_ctx::seq_mesh() const {
+  pnp::SeqMesh M;
+  M.nv = mesh.nv;
+  M.nt = mesh.nt;
+  M.tri = seq_tri.p;
+  M.vptr = seq_vptr.p;
+  M.vinc = seq_vinc.p;
+  M.xy = seq_xy.p;
+  return M;
+}
+
+pnp::SeqOp pnp_ctx::seq_op() const {
+  pnp::SeqOp P;
+  P.kind = kind;
+  P.nf = nf;
+  P.cyl = params.cylindrical;
+  P.pi = params.pi;
+  P.l_b = params.l_b;
+  P.c0 = params.c0;
+  P.tau = params.tau;
+  P.dt = seq_dt;
+  P.z = seq_z;
+  P.phi = seq_phi_h.empty() ? nullptr : seq_phi.p;
+  P.cp = seq_cp_h.empty() ? nullptr : seq_cp.p;
+  P.cm = seq_cm_h.empty() ? nullptr : seq_cm.p;
+  P.x_old = seq_xold_h.empty() ? nullptr : seq_xold.p;
+  return P;
+}
+
+// r = R(x), both external layout on the device (GridOperator::residual + constraints)
+int pnp_ctx::seq_residual(const double *x, double *r) {
+  int rc;
+  if ((rc = seq_prepare())) return rc;
+  const bool old = kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_DIFF_IMPLICIT_EULER;
+  hipError_t e = pnp::launch_seq_element(seq_mesh(), seq_op(), x, 0, seq_rl.p, seq_rlt.p,
+                                         seq_rlo.p, seq_jl.p, seq_jlt.p, seq_bptr.p, seq_bval.p,
+                                         stream);
+  if (e == hipSuccess)
+    e = pnp::launch_seq_residual_gather(seq_mesh(), nf, old ? 1 : 0, seq_rl.p, seq_rlt.p,
+                                        seq_rlo.p, seq_mask.p, r, stream);
+  return e == hipSuccess ? PNP_OK : hipfail(e, "seq residual");
+}
+
+// the CSR view = J(x) (GridOperator::jacobian + constrained rows to identity); fd: PDELab's
+// NumericalJacobianVolume
+int pnp_ctx::seq_jacobian(const double *x, bool fd) {
+  int rc;
+  if ((rc = seq_prepare()) || (rc = csr_structure())) return rc;
+  const bool onestep = kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_DIFF_IMPLICIT_EULER;
+  hipError_t e = pnp::launch_seq_element(seq_mesh(), seq_op(), x, fd ? 2 : 1, seq_rl.p,
+                                         seq_rlt.p, seq_rlo.p, seq_jl.p, seq_jlt.p, seq_bptr.p,
+                                         seq_bval.p, stream);
+  if (e == hipSuccess)
+    e = pnp::launch_seq_jacobian_gather(seq_mesh(), nf, seq_jl.p, onestep ? seq_jlt.p : nullptr,
+                                        csr_rowptr.p, csr_col.p,
+                                        seq_mask.p, csr_val.p, stream);
+  if (e != hipSuccess) return hipfail(e, "seq jacobian");
+  assembled = true;
+  csr_vals_valid = true;  // the CSR view holds this Jacobian; the k-form matrix does not
+  lu_valid = false;
+  split_of = 0;
+  amg_valid = false;
+  return PNP_OK;
+}
+
+double pnp_ctx::seq_dot(const double *a, const double *b, int &rc) {
+  rc = PNP_OK;
+  double h = 0;
+  hipError_t e = pnp::launch_seq_dot(nseq(), a, b, seq_dotv.p, stream);
+  if (e == hipSuccess) e = hipMemcpyAsync(&h, seq_dotv.p, 8, hipMemcpyDeviceToHost, stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(stream);
+  if (e != hipSuccess) rc = hipfail(e, "seq dot");
+  return h;
+}
 
 using pnp_ctx_t = pnp_ctx;
 
@@ -4514,123 +3018,112 @@ extern "C" int pnp_prec_apply(pnp_ctx *c, int32_t prec, const double *d, double 
     return PNP_OK;
   }
   if ((rc = c->upload_ext(d, c->nf, c->b.p, false))) return rc;
-  if (prec == PNP_PREC_ILU0 && (rc = c->ilu_factor())) return rc;
   if ((rc = c->precond(prec, c->b.p, c->z.p))) return rc;
-  if (prec == PNP_PREC_SSOR_NATURAL && (rc = c->nat_check())) return rc;
-  if (prec == PNP_PREC_ILU0 && (rc = c->ilu_flow_check())) return rc;
+  if ((rc = c->solve_checks(prec))) return rc;
   return c->download_ext(c->z.p, c->nf, v);
+}
+
+// ---- context options: one row per PNP_OPT_*, read by pnp_set_option and pnp_get_option ----------
+// on_set runs with the accepted value before it is stored; an error from it leaves the option as
+// it was
+static int opt_ilu_f32(pnp_ctx *c, int old, int now) {
+  if (old != now && c->split_of == 2) c->split_of = 0;  // re-split the factors in the new precision
+  return PNP_OK;
+}
+static int opt_ilu_fused(pnp_ctx *c, int, int) {
+  c->lu_valid = false;
+  if (c->split_of == 2) c->split_of = 0;
+  return PNP_OK;
+}
+static int opt_gmres_restart(pnp_ctx *c, int old, int now) {
+  if (old == now) return PNP_OK;
+  hipSetDevice(c->device);
+  c->gmres_free();
+  return PNP_OK;
+}
+static int opt_idr_s(pnp_ctx *c, int old, int now) {
+  if (old == now) return PNP_OK;
+  hipSetDevice(c->device);
+  c->idr_free();
+  return PNP_OK;
+}
+static int opt_seq_order(pnp_ctx *c, int old, int now) {
+  if (now && (c->degree > 1 || c->dist))
+    return c->fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: P1 contexts of one rank only");
+  if (old != now) {
+    c->assembled = false;  // the next Jacobian is assembled in the newly selected form
+    c->csr_vals_valid = false;
+    c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
+  }
+  return PNP_OK;
+}
+static int opt_matrix_free(pnp_ctx *c, int, int now) {
+  if (now && c->degree > 1)
+    return c->fail(PNP_E_STATE,
+                   "PNP_OPT_MATRIX_FREE: P1 contexts only (the matrix-free application walks the "
+                   "P1 vertex fans; P_k contexts assemble)");
+  if (!now && c->mf_lin) {
+    // the current Jacobian goes on as an assembled one: its values, if nobody needed them yet
+    hipSetDevice(c->device);
+    if (int rc = c->ensure_values()) return rc;
+    c->mf_lin = c->mf_diag_valid = false;
+  }
+  // the graphs_clear() at the top of pnp_set_option has dropped every captured BiCGSTAB graph
+  // and bumped graph_epoch: no graph captured in one form survives into the other, and none
+  // outlives an operator change made while the option was off (pnp_set_operator clears only
+  // while it is on)
+  return PNP_OK;
+}
+
+static const struct OptRow {
+  int id;
+  const char *name;
+  int lo, hi;
+  int pnp_ctx::*field;
+  int (*on_set)(pnp_ctx *, int old, int now);
+} kOptions[] = {
+    {PNP_OPT_GRAPH, "PNP_OPT_GRAPH", -1, 1, &pnp_ctx::graph_opt, nullptr},
+    {PNP_OPT_ILU_F32, "PNP_OPT_ILU_F32", 0, 3, &pnp_ctx::ilu_f32, opt_ilu_f32},
+    {PNP_OPT_ILU_FLOW, "PNP_OPT_ILU_FLOW", 0, 2, &pnp_ctx::ilu_flow_opt, nullptr},
+    {PNP_OPT_NAT_FLOW, "PNP_OPT_NAT_FLOW", -1, 1, &pnp_ctx::nat_flow_opt, nullptr},
+    {PNP_OPT_AMG_FALLBACK, "PNP_OPT_AMG_FALLBACK", 0, 1, &pnp_ctx::amg_fallback, nullptr},
+    {PNP_OPT_ILU_RETRY, "PNP_OPT_ILU_RETRY", 0, 1, &pnp_ctx::ilu_retry, nullptr},
+    {PNP_OPT_GMRES_RESTART, "PNP_OPT_GMRES_RESTART", pnp::kGmMinRestart, pnp::kGmMaxRestart,
+     &pnp_ctx::gm_restart, opt_gmres_restart},
+    {PNP_OPT_IDR_S, "PNP_OPT_IDR_S", pnp::kIdrMinS, pnp::kIdrMaxS, &pnp_ctx::idr_s, opt_idr_s},
+    {PNP_OPT_BICG_TWORED, "PNP_OPT_BICG_TWORED", -1, 1, &pnp_ctx::twored_opt, nullptr},
+    {PNP_OPT_SEQ_ORDER, "PNP_OPT_SEQ_ORDER", 0, 1, &pnp_ctx::seq_opt, opt_seq_order},
+    {PNP_OPT_MATRIX_FREE, "PNP_OPT_MATRIX_FREE", 0, 1, &pnp_ctx::mf_opt, opt_matrix_free},
+    // vals holds every plane either way: nothing to invalidate
+    {PNP_OPT_ASM_REUSE_CONST, "PNP_OPT_ASM_REUSE_CONST", 0, 1, &pnp_ctx::asm_reuse_opt, nullptr},
+    {PNP_OPT_JAC_FD, "PNP_OPT_JAC_FD", 0, 1, &pnp_ctx::fd_opt, nullptr},
+    {PNP_OPT_ILU_FUSED_FACTOR, "PNP_OPT_ILU_FUSED_FACTOR", 0, 1, &pnp_ctx::ilu_fused,
+     opt_ilu_fused},
+};
+
+static const OptRow *opt_row(int32_t option) {
+  for (const OptRow &r : kOptions)
+    if (r.id == option) return &r;
+  return nullptr;
 }
 
 extern "C" int pnp_set_option(pnp_ctx *c, int32_t option, int64_t value) {
   if (!c) return PNP_E_ARG;
   c->graphs_clear();
-  if (option == PNP_OPT_GRAPH) {
-    if (value < -1 || value > 1) return c->fail(PNP_E_ARG, "PNP_OPT_GRAPH takes -1, 0 or 1");
-    c->graph_opt = int(value);
-    return PNP_OK;
+  const OptRow *r = opt_row(option);
+  if (!r) return c->fail(PNP_E_ARG, "unknown option");
+  if (value < r->lo || value > r->hi) {  // "takes 0 or 1", "takes -1, 0 or 1", "takes 2 .. 128"
+    const int n = r->hi - r->lo;
+    const std::string a = std::to_string(r->lo), b = std::to_string(r->hi);
+    return c->fail(PNP_E_ARG, std::string(r->name) + " takes " + a +
+                                  (n == 1   ? " or " + b
+                                   : n == 2 ? ", " + std::to_string(r->lo + 1) + " or " + b
+                                            : " .. " + b));
   }
-  if (option == PNP_OPT_ILU_F32) {
-    if (value < 0 || value > 3) return c->fail(PNP_E_ARG, "PNP_OPT_ILU_F32 takes 0 .. 3");
-    if (c->ilu_f32 != int(value)) {
-      c->ilu_f32 = int(value);
-      if (c->split_of == 2) c->split_of = 0;  // re-split the factors in the new precision
-    }
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_FLOW) {
-    if (value < 0 || value > 2) return c->fail(PNP_E_ARG, "PNP_OPT_ILU_FLOW takes 0, 1 or 2");
-    c->ilu_flow_opt = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_NAT_FLOW) {
-    if (value < -1 || value > 1) return c->fail(PNP_E_ARG, "PNP_OPT_NAT_FLOW takes -1, 0 or 1");
-    c->nat_flow_opt = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_AMG_FALLBACK) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_AMG_FALLBACK takes 0 or 1");
-    c->amg_fallback = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_RETRY) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_ILU_RETRY takes 0 or 1");
-    c->ilu_retry = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_GMRES_RESTART) {
-    if (!pnp::gm_restart_valid(value))
-      return c->fail(PNP_E_ARG, "PNP_OPT_GMRES_RESTART takes 2 .. 128");
-    if (c->gm_restart != int(value)) {
-      hipSetDevice(c->device);
-      c->gmres_free();
-      c->gm_restart = int(value);
-    }
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_IDR_S) {
-    if (!pnp::idr_s_valid(value)) return c->fail(PNP_E_ARG, "PNP_OPT_IDR_S takes 1 .. 8");
-    if (c->idr_s != int(value)) {
-      hipSetDevice(c->device);
-      c->idr_free();
-      c->idr_s = int(value);
-    }
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_BICG_TWORED) {
-    if (value < -1 || value > 1) return c->fail(PNP_E_ARG, "PNP_OPT_BICG_TWORED takes -1, 0 or 1");
-    c->twored_opt = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_SEQ_ORDER) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER takes 0 or 1");
-    if (value && (c->degree > 1 || c->dist))
-      return c->fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: P1 contexts of one rank only");
-    if (c->seq_opt != int(value)) {
-      c->seq_opt = int(value);
-      c->assembled = false;  // the next Jacobian is assembled in the newly selected form
-      c->csr_vals_valid = false;
-      c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
-    }
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_MATRIX_FREE) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_MATRIX_FREE takes 0 or 1");
-    if (value && c->degree > 1)
-      return c->fail(PNP_E_STATE,
-                     "PNP_OPT_MATRIX_FREE: P1 contexts only (the matrix-free application walks the "
-                     "P1 vertex fans; P_k contexts assemble)");
-    if (!value && c->mf_lin) {
-      // the current Jacobian goes on as an assembled one: its values, if nobody needed them yet
-      hipSetDevice(c->device);
-      if (int rc = c->ensure_values()) return rc;
-      c->mf_lin = c->mf_diag_valid = false;
-    }
-    // the graphs_clear() at the top of this function has dropped every captured BiCGSTAB graph
-    // and bumped graph_epoch: no graph captured in one form survives into the other, and none
-    // outlives an operator change made while the option was off (pnp_set_operator clears only
-    // while it is on)
-    c->mf_opt = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ASM_REUSE_CONST) {
-    if (value != 0 && value != 1)
-      return c->fail(PNP_E_ARG, "PNP_OPT_ASM_REUSE_CONST takes 0 or 1");
-    c->asm_reuse_opt = int(value);  // vals holds every plane either way: nothing to invalidate
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_JAC_FD) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_JAC_FD takes 0 or 1");
-    c->fd_opt = int(value);
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_FUSED_FACTOR) {
-    if (value != 0 && value != 1) return c->fail(PNP_E_ARG, "PNP_OPT_ILU_FUSED_FACTOR takes 0 or 1");
-    c->ilu_fused = int(value);
-    c->lu_valid = false;
-    if (c->split_of == 2) c->split_of = 0;
-    return PNP_OK;
-  }
-  return c->fail(PNP_E_ARG, "unknown option");
+  if (r->on_set)
+    if (int rc = r->on_set(c, c->*(r->field), int(value))) return rc;
+  c->*(r->field) = int(value);
+  return PNP_OK;
 }
 
 extern "C" int pnp_set_create_option(int32_t option, int64_t value) {
@@ -4658,59 +3151,10 @@ extern "C" int pnp_get_create_option(int32_t option, int64_t *value) {
 
 extern "C" int pnp_get_option(pnp_ctx *c, int32_t option, int64_t *value) {
   if (!c || !value) return PNP_E_ARG;
-  if (option == PNP_OPT_ILU_F32) {
-    *value = c->ilu_f32;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_FUSED_FACTOR) {
-    *value = c->ilu_fused;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_GRAPH) {
-    *value = c->graph_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_JAC_FD) {
-    *value = c->fd_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_GMRES_RESTART) {
-    *value = c->gm_restart;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_BICG_TWORED) {
-    *value = c->twored_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_FLOW) {
-    *value = c->ilu_flow_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_AMG_FALLBACK) {
-    *value = c->amg_fallback;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ILU_RETRY) {
-    *value = c->ilu_retry;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_SEQ_ORDER) {
-    *value = c->seq_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_MATRIX_FREE) {
-    *value = c->mf_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_ASM_REUSE_CONST) {
-    *value = c->asm_reuse_opt;
-    return PNP_OK;
-  }
-  if (option == PNP_OPT_IDR_S) {
-    *value = c->idr_s;
-    return PNP_OK;
-  }
-  return c->fail(PNP_E_ARG, "unknown option");
+  const OptRow *r = opt_row(option);
+  if (!r) return c->fail(PNP_E_ARG, "unknown option");
+  *value = c->*(r->field);
+  return PNP_OK;
 }
 
 extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_assemblies) {

@@ -12,7 +12,7 @@ import pytest
 
 import pnp_amd as P
 from conftest import DATA
-from test_gpu import golden
+from test_gpu import golden, set_ops
 from test_gpu_multirank import run_ranks
 
 pytestmark = pytest.mark.gpu
@@ -66,6 +66,31 @@ def test_flow_pb_scalar_newton_bitwise():
     a, b = _both(ctx, lambda: (lambda u, r: (h(u), r["linear_iterations"]))(
         *ctx.newton(np.zeros(mesh.nv), prec=P.PREC_ILU0)))
     assert a == b
+    ctx.close()
+
+
+def test_flow_cg_poisson_bitwise():
+    """CG + ILU(0) on the Poisson operator (one field, symmetric), colour launches against both
+    dataflow forms (1 resident grid, 2 ticketed): each solve converges, and -- as everywhere in this
+    file -- iteration counts are equal and the solutions bitwise the same.  CG reads the dataflow
+    sweep's sticky timeout word after the solve like the other drivers (pnp_ctx::solve_checks)."""
+    z, mesh, par, orc = golden("pore_small_k0")
+    ctx = P.Context(mesh, par)
+    set_ops(z, ctx, orc, "poisson")
+    x = z["poisson_x"]
+    ctx.jacobian(x, export=False)
+    rhs = ctx.residual(x)
+
+    def solve():
+        sol, res = ctx.linear_solve(rhs, prec=P.PREC_ILU0, reduction=1e-10, maxit=2000,
+                                    method=P.METHOD_CG)
+        print(f"cg + ilu0, flow {ctx.get_option(P.OPT_ILU_FLOW)}: {res['iterations']} iterations, "
+              f"converged {res['converged']}, reduction {res['reduction']:.3e}")
+        assert res["converged"] == 1, res
+        return h(sol), res["iterations"]
+    for flow_on in (1, 2):
+        a, b = _both(ctx, solve, flow_on)
+        assert a == b, f"flow {flow_on}: {a} vs {b}"
     ctx.close()
 
 

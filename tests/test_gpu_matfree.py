@@ -453,6 +453,55 @@ def test_pk_contexts_refuse_the_option():
     ctx.close()
 
 
+# every PNP_OPT_* with its legal range (include/pnp_capi.h)
+OPTION_RANGES = {
+    P.OPT_ILU_F32: (0, 3), P.OPT_ILU_FUSED_FACTOR: (0, 1), P.OPT_JAC_FD: (0, 1),
+    P.OPT_BICG_TWORED: (-1, 1), P.OPT_AMG_FALLBACK: (0, 1), P.OPT_GRAPH: (-1, 1),
+    P.OPT_SEQ_ORDER: (0, 1), P.OPT_ILU_FLOW: (0, 2), P.OPT_NAT_FLOW: (-1, 1),
+    P.OPT_ILU_RETRY: (0, 1), P.OPT_GMRES_RESTART: (2, 128), P.OPT_MATRIX_FREE: (0, 1),
+    P.OPT_ASM_REUSE_CONST: (0, 1), P.OPT_IDR_S: (1, 8),
+}
+
+
+def test_every_option_round_trips():
+    """Every option takes each legal value and reads it back (PNP_OPT_NAT_FLOW too); one below and
+    one above the range is E_ARG and leaves the stored value alone; an unknown option is E_ARG."""
+    assert sorted(OPTION_RANGES) == list(range(1, 15))
+    z, mesh, par, orc = golden("pore_small_k0")
+    ctx = P.Context(mesh, par)
+    for opt, (lo, hi) in OPTION_RANGES.items():
+        default = ctx.get_option(opt)
+        assert lo <= default <= hi, (opt, default)
+        for v in range(lo, hi + 1):
+            ctx.set_option(opt, v)
+            assert ctx.get_option(opt) == v, (opt, v)
+            for bad in (lo - 1, hi + 1):
+                with pytest.raises(P.PnpError) as e:
+                    ctx.set_option(opt, bad)
+                assert e.value.code == P.E_ARG and " takes " in str(e.value), (opt, bad)
+                assert ctx.get_option(opt) == v, (opt, v, bad)
+        ctx.set_option(opt, default)
+    for call in (lambda: ctx.set_option(15, 0), lambda: ctx.get_option(15)):
+        with pytest.raises(P.PnpError) as e:
+            call()
+        assert e.value.code == P.E_ARG
+    ctx.close()
+
+
+def test_pk_contexts_refuse_p1_only_options():
+    """PNP_OPT_SEQ_ORDER = 1 (E_ARG) and PNP_OPT_MATRIX_FREE = 1 (E_STATE) on a P2 context: refused
+    with their codes, the options stay 0 and still take 0."""
+    z, mesh, par, orc = golden("pore_small_k0")
+    ctx = P.Context(mesh, par, degree=2)
+    for opt, code in ((P.OPT_SEQ_ORDER, P.E_ARG), (P.OPT_MATRIX_FREE, P.E_STATE)):
+        with pytest.raises(P.PnpError) as e:
+            ctx.set_option(opt, 1)
+        assert e.value.code == code, (opt, e.value)
+        assert ctx.get_option(opt) == 0
+        ctx.set_option(opt, 0)
+    ctx.close()
+
+
 def test_fd_jacobians_ignore_the_option():
     z, mesh, orc, ctx, op = mf_context("pore_small_k0", "pnp")
     ctx.set_option(P.OPT_JAC_FD, 1)

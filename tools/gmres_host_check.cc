@@ -34,7 +34,7 @@ struct Dense {
   }
 };
 
-// the host loop of ctx.cc gmres() without a preconditioner, on the same state functions
+// the host loop of krylov.cc gmres() without a preconditioner, on the same state functions
 static void solve(const Dense &A, const std::vector<double> &b, int m, double reduction, int maxit,
                   GmresState &S, std::vector<double> &hist, std::vector<double> &x) {
   const int n = A.n;

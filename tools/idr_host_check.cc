@@ -44,7 +44,7 @@ static double dot(const double *a, const double *b, int n) {
   return s;
 }
 
-// the shadow matrix as ctx.cc builds it: counter-based entries, modified Gram-Schmidt
+// the shadow matrix as krylov.cc builds it: counter-based entries, modified Gram-Schmidt
 static std::vector<double> shadow(int n, int s) {
   std::vector<double> P(size_t(n) * s);
   for (int j = 0; j < s; j++)
@@ -61,7 +61,7 @@ static std::vector<double> shadow(int n, int s) {
   return P;
 }
 
-// the host loop of ctx.cc idr() without a preconditioner, on the same state functions.  fake > 0:
+// the host loop of krylov.cc idr() without a preconditioner, on the same state functions.  fake > 0:
 // the recurrence's norm^2 is scaled by it (the residual-replacement path: the recurrence claims
 // convergence early, the true residual disagrees).
 static void solve(const Dense &A, const std::vector<double> &b, const std::vector<double> &P, int s,
