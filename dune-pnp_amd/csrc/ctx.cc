@@ -2579,6 +2579,35 @@ extern "C" int pnp_get_info(pnp_ctx *c, pnp_info *info) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int pnp_nfields(pnp_ctx *c) { return c ? c->nf : PNP_E_ARG; }
 
+// the part of an operator that depends on the mesh and the parameters only: the Dirichlet mask
+// (mask: every node, global order; lmask: owned rows) and the constant load (the Neumann flux of
+// alpha_boundary, times dt for PnpTOperator) on the owned rows.  nf fields as `kind` has them.
+void pnp_ctx::op_static(int k, int field, double dt, std::vector<uint8_t> &mask,
+                        std::vector<uint8_t> &lmask, std::vector<double> &lload) const {
+  const int nfk = (k == PNP_OP_PNP || k == PNP_OP_PNP_IMPLICIT_EULER) ? 3 : 1;
+  const int field0 = (k == PNP_OP_DIFF || k == PNP_OP_DIFF_IMPLICIT_EULER) ? field : 0;
+  if (degree > 1)
+    pnp::pk_dirichlet_mask(tmesh, pks, params, nfk, field0, mask);
+  else
+    pnp::dirichlet_mask(mesh, params, nfk, field0, mask);
+  std::vector<double> load(size_t(mesh.nv) * nfk, 0.0);
+  if (k == PNP_OP_PNP || k == PNP_OP_PNP_IMPLICIT_EULER || k == PNP_OP_PB || k == PNP_OP_POISSON) {
+    if (degree > 1)
+      pnp::pk_neumann_load(tmesh, pks, params, nfk, 0, load);
+    else
+      pnp::neumann_load(mesh, params, nfk, 0, load);
+    if (k == PNP_OP_PNP_IMPLICIT_EULER)
+      for (auto &v : load) v *= dt;
+  }
+  lmask.resize(size_t(L.n_owned) * nfk);
+  lload.resize(size_t(L.n_owned) * nfk);
+  for (int i = 0; i < L.n_owned; i++)
+    for (int f = 0; f < nfk; f++) {
+      lmask[size_t(i) * nfk + f] = mask[size_t(L.l2g[i]) * nfk + f];
+      lload[size_t(i) * nfk + f] = load[size_t(L.l2g[i]) * nfk + f];
+    }
+}
+
 extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   if (!c || !a) return PNP_E_ARG;
   // no graphs_clear() here: the operator's pattern and mask pointer are in the graph key; a change
@@ -2625,30 +2654,13 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   const pnp::LocalLayout &L = c->L;
   int nf = c->nf;
   // Dirichlet mask and constant load (Neumann flux of alpha_boundary), owned rows
-  int field0 = (kind == PNP_OP_DIFF || kind == PNP_OP_DIFF_IMPLICIT_EULER) ? a->field : 0;
-  std::vector<uint8_t> mask;
-  if (c->degree > 1)
-    pnp::pk_dirichlet_mask(c->tmesh, c->pks, c->params, nf, field0, mask);
-  else
-    pnp::dirichlet_mask(m, c->params, nf, field0, mask);
-  std::vector<double> load(size_t(m.nv) * nf, 0.0);
-  if (kind == PNP_OP_PNP || kind == PNP_OP_PNP_IMPLICIT_EULER || kind == PNP_OP_PB ||
-      kind == PNP_OP_POISSON) {
-    if (c->degree > 1)
-      pnp::pk_neumann_load(c->tmesh, c->pks, c->params, nf, 0, load);
-    else
-      pnp::neumann_load(m, c->params, nf, 0, load);
-    if (kind == PNP_OP_PNP_IMPLICIT_EULER)
-      for (auto &v : load) v *= a->dt;
-  }
-  std::vector<uint8_t> lmask(size_t(L.n_owned) * nf);
-  std::vector<double> lload(size_t(L.n_owned) * nf);
-  for (int i = 0; i < L.n_owned; i++)
-    for (int f = 0; f < nf; f++) {
-      lmask[size_t(i) * nf + f] = mask[size_t(L.l2g[i]) * nf + f];
-      lload[size_t(i) * nf + f] = load[size_t(L.l2g[i]) * nf + f];
-      if (a->c_extra) lload[size_t(i) * nf + f] += a->c_extra[size_t(f) * m.nv + L.l2g[i]];
-    }
+  std::vector<uint8_t> mask, lmask;
+  std::vector<double> lload;
+  c->op_static(kind, a->field, a->dt, mask, lmask, lload);
+  if (a->c_extra)
+    for (int i = 0; i < L.n_owned; i++)
+      for (int f = 0; f < nf; f++)
+        lload[size_t(i) * nf + f] += a->c_extra[size_t(f) * m.nv + L.l2g[i]];
   CK(hipMemcpy(c->dmask.p, lmask.data(), lmask.size(), hipMemcpyHostToDevice), "dmask");
   {  // the P1 assembly's flag byte per row: its mask bits, and whether its load is to be read --
      // any entry that is not bitwise +0.0 (-0.0 too); implicit Euler: every row, the device mass
@@ -3255,6 +3267,13 @@ extern "C" int pnp_ion_flux(pnp_ctx *c, const double *x, int32_t nsurf, double *
   } else if (c->nf != 3) {
     return c->fail(PNP_E_STATE, "ion flux of the context state needs a 3-field (PNP) operator");
   }
+  return c->ion_flux_dev(xd, nsurf, ip, im);
+}
+
+// the currents of the 3-field interleaved device state xd (internal layout, with ghosts)
+int pnp_ctx::ion_flux_dev(const double *xd, int nsurf, double *ip, double *im) {
+  pnp_ctx *c = this;
+  int rc;
   const int ns = int(c->fseg_group.size());
   if (c->degree > 1)
     CK(pnp::launch_pk_ion_flux(c->dl, c->pkd, ns, c->d_fseg.p, xd, c->params.cylindrical,

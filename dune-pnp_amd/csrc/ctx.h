@@ -1,6 +1,6 @@
 // The context behind the C ABI (include/pnp_capi.h): its data, the small accessors and the
-// declarations of the member functions defined in ctx.cc (everything but the linear solvers)
-// and krylov.cc (the linear solvers).
+// declarations of the member functions defined in ctx.cc (everything but the linear solvers),
+// krylov.cc (the linear solvers) and md.cc (the operator-split time loop).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -635,6 +635,31 @@ struct pnp_ctx {
   int idr_shadow_build();
   int idr_alloc();
   int idr(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res);
+
+  // ---- the operator-split time loop (pnp_md_run, md.cc) -------------------------
+  // what pnp_set_operator computes from the mesh and the parameters alone (ctx.cc)
+  void op_static(int kind, int field, double dt, std::vector<uint8_t> &mask,
+                 std::vector<uint8_t> &lmask, std::vector<double> &lload) const;
+  int ion_flux_dev(const double *xd, int nsurf, double *ip, double *im);
+  // one operator of the loop: its static part, computed once per run and kept on the device
+  struct MdOp {
+    int kind = -1, field = 0;
+    double z = 0;
+    std::vector<uint8_t> gmask;         // every node, global order
+    std::vector<uint8_t> hmask, hflag;  // owned rows; whole SELL chunks (as rowflag)
+    DBuf<uint8_t> mask, flag;
+    DBuf<double> load;                  // owned rows
+  };
+  struct MdRun;  // the run's resident state (md.cc)
+  int md_op_build(MdOp &op, int kind, int field, double z);
+  int md_activate(const MdOp &op, double dt, const double *a0, const double *a1);
+  int md_cvec(const MdOp &op, double s, const double *r1, const double *xold);
+  int md_residual_of(const MdOp &op, const double *xdev);
+  int md_linear_problem(MdRun &R, double *xvec, bool jac, double reduction, bool diffusion);
+  int md_alexander2(MdRun &R, double *cvecx, const MdOp &ie, const MdOp &sp);
+  int md_poisson(MdRun &R);
+  int md_run(double *u, const pnp_md_opts &o, int nsurf, int cap, double *t_out, double *ip,
+             double *im, pnp_md_result &res, bool devptr);
 
   // ---- reference-order mode (PNP_OPT_SEQ_ORDER) ------------------------------------------------
   // The reference's single-rank arithmetic in its order (seq_order.hip): element-order assembly

@@ -700,4 +700,17 @@ hipError_t launch_pk_ion_flux(const DevLayout &L, const PkDev &P, int ns, const 
 hipError_t launch_slot_store_probe(const DevLayout &L, const int *order, double *val,
                                    hipStream_t s);
 
+// ---- the device-resident operator-split loop (md.hip; pnp_md_run) ------------------------------
+// scalar vectors in the internal layout, n rows each
+// x -= z (StationaryLinearProblemSolver::apply's update, owned rows)
+hipError_t launch_md_sub(int n, const double *z, double *x, hipStream_t s);
+// cvec = load + scale r1, the product rounded and then the sum (r1 null: cvec = load)
+hipError_t launch_md_load(int n, const double *load, double scale, const double *r1, double *cvec,
+                          hipStream_t s);
+// phi, c+, c- <-> the 3-field interleaved vector x3 (the flux kernels' input; upload / download)
+hipError_t launch_md_pack(int n, const double *phi, const double *cp, const double *cm, double *x3,
+                          hipStream_t s);
+hipError_t launch_md_unpack(int n, const double *x3, double *phi, double *cp, double *cm,
+                            hipStream_t s);
+
 }  // namespace pnp

@@ -16,6 +16,11 @@
 //                                 Krylov method, default bicgstab; m: the GMRES restart length, 2 .. 128,
 //                                 default 30; s: IDR(s)'s shadow space dimension, 1 .. 8, default 4)
 //                 [--md-reduction r]
+//                 [--md-loop host|device]  (md mode: the time loop driven from here through the
+//                                 host-pointer ABI, the default, or pnp_md_run with the state
+//                                 resident on the device; the same files bit for bit)
+//                 [--md-reuse 0|1]  (with --md-loop device: stage 2 of each Alexander2 step keeps
+//                                 stage 1's matrix and preconditioner set-up; default 1)
 //                 [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]
 //                 (bcgs_ssork, the reference's default: ISTL SeqSSOR in the lexicographic order,
 //                  PNP_PREC_SSOR_NATURAL; bcgs_ssork_mc: the multicolour sweep, same method, other order)
@@ -63,7 +68,7 @@ static void usage() {
       "                [--device d] [--matrix-free] [--asm-full]\n"
       "                [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]\n"
       "                [--amg-smoother ssor|ilu0|jacobi]\n"
-      "                [--out prefix] [--md-reduction r]\n"
+      "                [--out prefix] [--md-reduction r] [--md-loop host|device] [--md-reuse 0|1]\n"
       "                [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]\n"
       "                [--abs-limit a] [--dump-steps n1,n2,...] [--degree 1|2|3]\n"
       "                [--reference-solvers]  (PB: ISTL SeqSSOR in DOF order, PNP: no preconditioner)\n"
@@ -106,7 +111,7 @@ static void linear_problem(pnp_gpu::Context &ctx, pnp_gpu::GridOperator<V> &go,
 //   (:424-451) as "time ip_0 im_0 ip_1 im_1 ..." with each ip/im a 2-vector (component 1 = 0).
 static void md_loop(pnp_gpu::Context &ctx, const pnp_gpu::Sysparams &s, V &u, int nv, int rank,
                     int steps, double md_reduction, int prec, int method,
-                    const std::string &out) {
+                    const std::string &out, bool device_loop, int reuse) {
   V phi(u.begin(), u.begin() + nv), cp(u.begin() + nv, u.begin() + 2 * size_t(nv)),
       cm(u.begin() + 2 * size_t(nv), u.end());
   const double a = 1.0 - 0.5 * std::sqrt(2.0), dt = s.cfg.tau;
@@ -119,6 +124,26 @@ static void md_loop(pnp_gpu::Context &ctx, const pnp_gpu::Sysparams &s, V &u, in
   std::ofstream current;
   if (rank == 0) current.open(out.empty() ? std::string("current.dat") : out + "_current.dat");
   current.precision(17);
+  if (device_loop) {  // the same loop inside the library, its state resident on the device
+    pnp_gpu::MdLoop<V> loop(ctx, ls);
+    loop.setReductions(red_diff, red_pois);
+    loop.setFrequencies(upd, outf);
+    loop.setReuse(reuse != 0);
+    loop.apply(u, dt, nsteps, nsurf);
+    if (rank == 0)
+      for (const auto &o : loop.outputs()) {
+        current << o.time;
+        for (int g = 0; g < nsurf; g++) current << " " << o.ip[g] << " 0 " << o.im[g] << " 0";
+        current << std::endl;
+      }
+    const pnp_md_result &r = loop.result();
+    if (rank == 0)
+      std::printf("md loop on the device: %d steps, %d + %d solves, %d linear iterations, %d "
+                  "assemblies, %d preconditioner set-ups, %.3f s\n",
+                  r.steps_done, r.diffusion_solves, r.poisson_solves, r.linear_iterations,
+                  r.assemblies, r.prec_setups, r.elapsed);
+    return;
+  }
   auto poisson = [&]() {
     pnp_gpu::Operator op(PNP_OP_POISSON);
     op.args.cp = cp.data();
@@ -202,6 +227,8 @@ int main(int argc, char **argv) {
   std::vector<int> dump_steps;  // instationary: write the state after these steps (1-based)
   // md mode: PbLS, the compile-time LINEARSOLVER of src/instationary_pnp_from_pb_md.hh:20-32,188-211
   std::string linsolver = "bcgs_ssork";
+  std::string md_loop_mode = "host";  // md mode: who drives the time loop
+  int md_reuse = 1;
   std::string method = "bicgstab";  // the Krylov method of the PNP phases (stationary / instationary)
   int restart = 0;                  // > 0: PNP_OPT_GMRES_RESTART
   int idr_s = 0;                    // > 0: PNP_OPT_IDR_S
@@ -221,6 +248,8 @@ int main(int argc, char **argv) {
     else if (a == "--device") device = std::atoi(next().c_str());
     else if (a == "--out") out = next();
     else if (a == "--md-reduction") md_reduction = std::atof(next().c_str());
+    else if (a == "--md-loop") md_loop_mode = next();
+    else if (a == "--md-reuse") md_reuse = std::atoi(next().c_str());
     else if (a == "--linear-solver") linsolver = next();
     else if (a == "--abs-limit") abs_limit = std::atof(next().c_str());
     else if (a == "--degree") degree = std::atoi(next().c_str());
@@ -396,7 +425,10 @@ int main(int argc, char **argv) {
       else if (linsolver == "cg_amg_ssor") lmethod = PNP_METHOD_CG, lprec = PNP_PREC_AMG;
       else if (linsolver != "bcgs_ssork")
         throw pnp_gpu::Error(PNP_E_ARG, "unknown --linear-solver " + linsolver);
-      md_loop(ctx, s, u, nv, rank, steps, md_reduction, lprec, lmethod, out);
+      if (md_loop_mode != "host" && md_loop_mode != "device")
+        throw pnp_gpu::Error(PNP_E_ARG, "unknown --md-loop " + md_loop_mode);
+      md_loop(ctx, s, u, nv, rank, steps, md_reduction, lprec, lmethod, out,
+              md_loop_mode == "device", md_reuse);
     } else {
       usage();
       return 1;

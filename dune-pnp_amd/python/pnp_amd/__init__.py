@@ -10,6 +10,8 @@ objects and call sequence (src/stationary_pnp_from_pb.hh:93-369):
     ISTLBackend_NOVLP_BCGS_*.apply    -> Context.linear_solve(rhs, prec=...)
     Newton::apply                     -> Context.newton(u, ...)
     interpolate(BCExtension)          -> Context.initial_state(phi_pb)
+    OneStepMethod<Alexander2> + the md time loop -> Context.md_run(u, dt, nsteps, ...)
+                                                    (src/instationary_pnp_from_pb_md.hh:411-454)
 
 Everything numeric runs in the HIP kernels of libpnp_amd.so; there is no Python or CPU fallback:
 if the shared library is missing or the GPU is absent, the calls raise.
@@ -235,6 +237,20 @@ class _NewtonResult(C.Structure):
                 ("first_defect", C.c_double), ("defect", C.c_double), ("elapsed", C.c_double),
                 ("assemble_seconds", C.c_double), ("solve_seconds", C.c_double),
                 ("linear_fallbacks", C.c_int32), ("precision_retries", C.c_int32)]
+
+
+class _MdOpts(C.Structure):
+    _fields_ = [("dt", C.c_double), ("t0", C.c_double), ("nsteps", C.c_int32),
+                ("potential_update_freq", C.c_int32), ("output_freq", C.c_int32),
+                ("red_diffusion", C.c_double), ("red_poisson", C.c_double),
+                ("linear", _SolveOpts), ("reuse", C.c_int32)]
+
+
+class _MdResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("steps_done", C.c_int32),
+                ("diffusion_solves", C.c_int32), ("poisson_solves", C.c_int32),
+                ("linear_iterations", C.c_int32), ("assemblies", C.c_int32),
+                ("prec_setups", C.c_int32), ("noutputs", C.c_int32), ("elapsed", C.c_double)]
 
 
 class _Timers(C.Structure):
@@ -731,6 +747,45 @@ class Context:
             raise PnpError(E_ARG, "ion_flux needs a 3-field state")
         self._ck(lib().pnp_ion_flux(self.h, _ptr(xv), n, _ptr(ip), _ptr(im)))
         return ip, im
+
+    def md_run(self, u, dt, nsteps, potential_update_freq=1, output_freq=1, t0=0.0,
+               red_diffusion=1e-5, red_poisson=1e-10, prec=PREC_SSOR_NATURAL, method=0,
+               maxit=5000, check_every=8, reuse=1, nsurf=None, cap=None, device_ptr=False):
+        """pnp_md_run: the operator-split time loop (instationary_pnp_md,
+        src/instationary_pnp_from_pb_md.hh:411-454) with its state resident on the device.
+        u: [phi | c+ | c-] over the context's nodes (device_ptr: the address of 3 * nn device
+        doubles, updated in place).  cap: output records kept (default: all nsteps could produce).
+        Returns (u, t, ip, im, result): the final state (None with device_ptr), the kept output
+        times [k], currents [k, nsurf], and the pnp_md_result fields as a dict.  A failed solve
+        does not raise: result["status"] is E_NOT_CONVERGED / E_BREAKDOWN."""
+        ns = int(nsurf if nsurf is not None else len(self.params.surfaces))
+        outf = max(1, int(output_freq))
+        if cap is None:
+            cap = (max(0, int(nsteps)) + outf - 1) // outf
+        cap = int(cap)
+        t = np.zeros(max(cap, 0))
+        ip = np.zeros((max(cap, 0), ns))
+        im = np.zeros((max(cap, 0), ns))
+        if device_ptr:
+            uv, up = None, C.c_void_p(int(u))
+        else:
+            uv = np.ascontiguousarray(u, dtype=np.float64).copy()
+            if uv.size != 3 * self.nn:
+                raise PnpError(E_ARG, "md_run needs a 3-field state")
+            up = _ptr(uv)
+        o = _MdOpts(dt, t0, int(nsteps), int(potential_update_freq), int(output_freq),
+                    red_diffusion, red_poisson,
+                    _SolveOpts(prec, 0.0, int(maxit), int(check_every), int(method)), int(reuse))
+        r = _MdResult()
+        self._ck(lib().pnp_md_run(self.h, up, C.byref(o), ns, cap,
+                                  _ptr(t) if cap > 0 else None, _ptr(ip) if cap > 0 else None,
+                                  _ptr(im) if cap > 0 else None, C.byref(r),
+                                  DEVICE_PTRS if device_ptr else 0))
+        res = {k: getattr(r, k) for k, _ in _MdResult._fields_}
+        if res["status"] == OK:
+            self.nf = 1  # the Poisson operator of the last solve is the context's operator now
+        n = min(cap, res["noutputs"])
+        return uv, t[:n], ip[:n], im[:n], res
 
     def newton(self, u, reduction=1e-9, abs_limit=1e-12, min_linear_reduction=1e-8, maxit=50,
                line_search_maxit=500, prec=PREC_NONE, linear_maxit=20000, check_every=8,

@@ -633,6 +633,51 @@ int pnp_initial_state(pnp_ctx *ctx, const double *phi_pb, double *x0);
  * layout) or NULL for the context's current 3-field state.  Collective on multi-GPU. */
 int pnp_ion_flux(pnp_ctx *ctx, const double *x, int32_t nsurf, double *ip, double *im);
 
+/* The operator-split time loop instationary_pnp_md (src/instationary_pnp_from_pb_md.hh:411-454)
+ * with its state resident on the device: per step i one OneStepMethod<Alexander2> step
+ * (a = 1 - sqrt(2)/2, :372-386) for c+ (z = +1, field 1), then for c- (z = -1, field 2), t += dt,
+ * the PoissonOperator problem if i % potential_update_freq == 0 (:421-423), the ion currents
+ * (calcIonFlux, :424-451) if i % output_freq == 0; after the last step one more Poisson solve.
+ * Alexander2 per ion:
+ *   stage 1: M(u1) - M(u0) + a dt R(u1) = 0          (PNP_OP_DIFF_IMPLICIT_EULER, dt = a dt)
+ *   r1 = R(u1) of PNP_OP_DIFF
+ *   stage 2: the same operator with c_extra = ((1 - a) dt) r1, started from u1
+ * each stage, and each Poisson problem, one StationaryLinearProblemSolver::apply (:349-350,
+ * :383-386): r = R(x), A = J(x), A z = r to the reduction, x -= z.  The right-hand side is the
+ * residual-only evaluation, so the run computes bit for bit what the same sequence of
+ * pnp_set_operator / pnp_residual / pnp_jacobian / pnp_linear_solve / pnp_ion_flux calls does. */
+typedef struct {
+  double dt, t0;                       /* step (the driver passes cfg.tau) and start time */
+  int32_t nsteps, potential_update_freq, output_freq;   /* freqs < 1 count as 1 */
+  double red_diffusion, red_poisson;   /* linear reductions (reference: 1e-5, 1e-10) */
+  pnp_solve_opts linear;               /* method, prec, maxit, check_every; reduction ignored */
+  int32_t reuse;                       /* 1: stage 2 keeps stage 1's matrix and set-up (the same
+                                          a dt, z, phi and mask, and the operator is linear) */
+} pnp_md_opts;
+typedef struct {
+  int32_t status, steps_done;          /* status: PNP_OK, PNP_E_NOT_CONVERGED, PNP_E_BREAKDOWN */
+  int32_t diffusion_solves, poisson_solves, linear_iterations;
+  int32_t assemblies, prec_setups;     /* Jacobian value assemblies / preconditioner set-ups: the
+                                          solves that set their preconditioner up on a newly
+                                          assembled matrix (PNP_PREC_NONE's empty one included) */
+  int32_t noutputs;                    /* output records produced (may exceed cap) */
+  double elapsed;
+} pnp_md_result;
+/* u: [phi | c+ | c-] over the context's nodes, external layout, 3 x nv_global, in and out (host, or
+ * device memory with PNP_DEVICE_PTRS in flags).  On a multi-rank context every rank passes the
+ * global vector and gets its owned entries back, as pnp_newton does (pnp_sync_vector(u, 3) makes
+ * it global); collective.  Output k < min(cap, noutputs): t_out[k], ip[k*nsurf + g],
+ * im[k*nsurf + g] (host; the arrays may be NULL with cap 0).
+ * A solve that breaks down or stops unconverged ends the run: res->status says which, the function
+ * still returns PNP_OK, res->steps_done counts the completed steps and u is the state after the
+ * last completed one.  P1 and P_k contexts, every transport, every method and preconditioner
+ * pnp_linear_solve takes on scalar operators; PNP_OPT_MATRIX_FREE keeps its meaning.  Not in
+ * reference-order mode (PNP_OPT_SEQ_ORDER: PNP_E_STATE).  PNP_E_ARG: nsteps < 0, dt <= 0, NULL
+ * u / opts / res, cap > 0 with a NULL array.  After the call the context's operator is the Poisson
+ * operator of the last solve. */
+int pnp_md_run(pnp_ctx *ctx, double *u, const pnp_md_opts *opts, int32_t nsurf, int32_t cap,
+               double *t_out, double *ip, double *im, pnp_md_result *res, int32_t flags);
+
 /* ---- device-resident hot path (benchmarks: inputs already in HBM) --------------------------- */
 /* upload x (external layout) into the context's state vector */
 int pnp_state_set(pnp_ctx *ctx, const double *x);

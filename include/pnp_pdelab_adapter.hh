@@ -335,6 +335,59 @@ class Newton {
   int verbose_ = 0;
 };
 
+// The operator-split time loop of src/instationary_pnp_from_pb_md.hh:411-454 -- per step one
+// OneStepMethod<Alexander2>::apply for c+ and one for c-, the Poisson problem every
+// potentialUpdateFreq steps, calcIonFlux every outputFreq steps -- as one call with the state
+// resident on the device (pnp_md_run).  u = [phi | c+ | c-]; the linear solver's method,
+// preconditioner and iteration limit come from the backend.
+template <class V>
+class MdLoop {
+ public:
+  struct Output {
+    double time;
+    std::vector<double> ip, im;  // per boundary group
+  };
+  MdLoop(Context &ctx, BiCGStabBackend<V> &ls) : ctx_(ctx), ls_(ls) {}
+  void setReductions(double diffusion, double poisson) {
+    o_.red_diffusion = diffusion;
+    o_.red_poisson = poisson;
+  }
+  void setFrequencies(int potential_update, int output) {
+    o_.potential_update_freq = potential_update;
+    o_.output_freq = output;
+  }
+  void setReuse(bool on) { o_.reuse = on ? 1 : 0; }  // stage 2 keeps stage 1's matrix and set-up
+  // nsteps steps of size dt from time t0; throws on a failed solve (u: the last completed step)
+  void apply(V &u, double dt, int nsteps, int nsurf, double t0 = 0.0) {
+    o_.dt = dt;
+    o_.t0 = t0;
+    o_.nsteps = nsteps;
+    o_.linear = pnp_solve_opts{ls_.prec(), 0.0, ls_.maxit(), 8, ls_.method()};
+    const int outf = o_.output_freq < 1 ? 1 : o_.output_freq;
+    const int cap = nsteps > 0 ? (nsteps + outf - 1) / outf : 0;
+    std::vector<double> t(size_t(cap) + 1), ip(size_t(cap) * nsurf + 1), im(size_t(cap) * nsurf + 1);
+    res_ = pnp_md_result{};
+    check(pnp_md_run(ctx_.get(), data(u), &o_, nsurf, cap, t.data(), ip.data(), im.data(), &res_, 0),
+          ctx_.get());
+    out_.clear();
+    for (int k = 0; k < res_.noutputs && k < cap; k++)
+      out_.push_back(Output{t[size_t(k)],
+                            {ip.begin() + size_t(k) * nsurf, ip.begin() + size_t(k + 1) * nsurf},
+                            {im.begin() + size_t(k) * nsurf, im.begin() + size_t(k + 1) * nsurf}});
+    if (res_.status != PNP_OK) throw Error(res_.status, "md loop: a linear solve failed");
+  }
+  const std::vector<Output> &outputs() const { return out_; }
+  const pnp_md_result &result() const { return res_; }
+
+ private:
+  Context &ctx_;
+  BiCGStabBackend<V> &ls_;
+  pnp_md_opts o_{0.0, 0.0, 0, 1, 1, 1e-5, 1e-10, {PNP_PREC_NONE, 0.0, 5000, 8, PNP_METHOD_BICGSTAB},
+                 1};
+  pnp_md_result res_{};
+  std::vector<Output> out_;
+};
+
 }  // namespace pnp_gpu
 
 #endif
