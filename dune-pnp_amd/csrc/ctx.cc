@@ -410,14 +410,8 @@ int pnp_ctx::assemble(const double *xdev, int jac) {
     te(T_ASM, t0);
   }
   if (jac) {
-    assembled = true;
-    lu_valid = false;
-    split_of = 0;
-    amg_valid = false;
-    csr_vals_valid = false;
+    jacobian_stored(mf);
     after_solve = false;
-    mf_lin = vals_stale = mf;
-    mf_diag_valid = false;
     if (!mf) value_assemblies++;
   }
   return PNP_OK;
@@ -1124,16 +1118,10 @@ int pnp_ctx::set_fd(bool on) {
   int rc;
   // P_k: the element kernel differentiates by itself; scalar blocks need no FD value layout
   if (on && !fd_built && degree == 1 && (rc = fd_build())) return rc;
-  const int base = kind == PNP_OP_PNP ? pnp::kPatPnp
-                                      : (kind == PNP_OP_PNP_IMPLICIT_EULER ? pnp::kPatPnpIE
-                                                                          : pnp::kPatScalar);
-  pat = (on && nf == 3) ? (base | pnp::kPatFD) : base;
+  pat = (on && nf == 3) ? (base_pat(kind) | pnp::kPatFD) : base_pat(kind);
   nks = pnp::nks_of(pat);
   fd_mode = on;
-  assembled = false;
-  lu_valid = false;
-  split_of = 0;
-  amg_valid = false;
+  jacobian_drop();           // assemble(), the only caller, stores one next or fails
   vals_const_valid = false;  // another value layout, zeroed below
   if (on && degree == 1) {
     // one-step operators keep two matrices per element (spatial, temporal: fd_jacobian.hip)
@@ -1738,11 +1726,7 @@ int pnp_ctx::seq_jacobian(const double *x, bool fd) {
                                         csr_rowptr.p, csr_col.p,
                                         seq_mask.p, csr_val.p, stream);
   if (e != hipSuccess) return hipfail(e, "seq jacobian");
-  assembled = true;
-  csr_vals_valid = true;  // the CSR view holds this Jacobian; the k-form matrix does not
-  lu_valid = false;
-  split_of = 0;
-  amg_valid = false;
+  seq_jacobian_stored();  // the CSR view holds this Jacobian; the k-form matrix does not
   return PNP_OK;
 }
 
@@ -2584,7 +2568,7 @@ extern "C" int pnp_nfields(pnp_ctx *c) { return c ? c->nf : PNP_E_ARG; }
 // alpha_boundary, times dt for PnpTOperator) on the owned rows.  nf fields as `kind` has them.
 void pnp_ctx::op_static(int k, int field, double dt, std::vector<uint8_t> &mask,
                         std::vector<uint8_t> &lmask, std::vector<double> &lload) const {
-  const int nfk = (k == PNP_OP_PNP || k == PNP_OP_PNP_IMPLICIT_EULER) ? 3 : 1;
+  const int nfk = nfields_of(k);
   const int field0 = (k == PNP_OP_DIFF || k == PNP_OP_DIFF_IMPLICIT_EULER) ? field : 0;
   if (degree > 1)
     pnp::pk_dirichlet_mask(tmesh, pks, params, nfk, field0, mask);
@@ -2608,6 +2592,68 @@ void pnp_ctx::op_static(int k, int field, double dt, std::vector<uint8_t> &mask,
     }
 }
 
+// a row's mask bits, and whether its load is to be read: every row of an implicit-Euler operator,
+// else any load entry that is not bitwise +0.0 (-0.0 too), and any such entry of the caller's
+// c_extra (external layout, or null) whatever the sum came to
+std::vector<uint8_t> pnp_ctx::row_flags(int nfk, bool ie, const std::vector<uint8_t> &lmask,
+                                        const std::vector<double> &lload,
+                                        const double *c_extra) const {
+  std::vector<uint8_t> flag(rowflag.n, 0);
+  for (int i = 0; i < L.n_owned; i++) {
+    unsigned fl = ie ? pnp::kRowFlagLoad : 0;
+    for (int f = 0; f < nfk; f++) {
+      if (lmask[size_t(i) * nfk + f]) fl |= 1u << f;
+      uint64_t bits;
+      std::memcpy(&bits, &lload[size_t(i) * nfk + f], sizeof bits);
+      if (bits) fl |= pnp::kRowFlagLoad;
+      if (c_extra) {
+        std::memcpy(&bits, &c_extra[size_t(f) * mesh.nv + L.l2g[i]], sizeof bits);
+        if (bits) fl |= pnp::kRowFlagLoad;
+      }
+    }
+    flag[i] = uint8_t(fl);
+  }
+  return flag;
+}
+
+int pnp_ctx::op_activate(int k, double dt, double z) {
+  kind = k;
+  fd_mode = false;  // the next Jacobian picks its form (set_fd)
+  nf = nfields_of(k);
+  pat = base_pat(k);
+  nvb = pnp::popc9(pat);
+  nks = pnp::nks_of(pat);
+  jacobian_drop();
+  // a captured matrix-free application holds the operator's scalar arguments (dt, valency, ...) by
+  // value, which the graph key does not see
+  if (mf_opt) graphs_clear();
+  // SELL padding slots point at the row itself and are never written by the assembly, so they
+  // must hold zeros in the k-form layout of THIS operator (the SpMV multiplies them)
+  vals_const_valid = false;
+  hipError_t e = hipMemsetAsync(vals.p, 0, sizeof(double) * size_t(L.nslots) * nks, stream);
+  if (e != hipSuccess) return hipfail(e, "clear matrix");
+  seq_op_valid = false;
+  seq_dt = dt;
+  seq_z = z;
+  dl.dmask = dmask.p;
+  aa = pnp::AsmArgs{};
+  aa.kind = k;  // PNP_OP_* == pnp::OP_* by construction
+  aa.l_b = params.l_b;
+  aa.c0 = params.c0;
+  aa.tau = params.tau;
+  aa.pi = params.pi;
+  aa.dt = dt;
+  aa.z = z;
+  aa.cylindrical = params.cylindrical;
+  aa.aux0 = aux0.p;
+  aa.aux1 = aux1.p;
+  aa.cvec = cvec.p;
+  aa.dmask = dmask.p;
+  aa.rowflag = rowflag.p;
+  aa.vals = vals.p;
+  return PNP_OK;
+}
+
 extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   if (!c || !a) return PNP_E_ARG;
   // no graphs_clear() here: the operator's pattern and mask pointer are in the graph key; a change
@@ -2629,27 +2675,8 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
     return c->fail(PNP_E_ARG,
                    "PnpOperator / PnpTOperator are P1 in the reference (Pk2DLocalFiniteElementMap<..., 1>, "
                    "src/stationary_pnp_from_pb.hh:206-208); P_k contexts take PB, Poisson and diffusion");
-  c->kind = kind;
-  c->fd_mode = false;  // the next Jacobian picks its form (set_fd)
-  c->nf = (kind == PNP_OP_PNP || kind == PNP_OP_PNP_IMPLICIT_EULER) ? 3 : 1;
-  c->pat = kind == PNP_OP_PNP ? pnp::kPatPnp
-                              : (kind == PNP_OP_PNP_IMPLICIT_EULER ? pnp::kPatPnpIE : pnp::kPatScalar);
-  c->nvb = pnp::popc9(c->pat);
-  c->nks = pnp::nks_of(c->pat);
-  c->assembled = false;
-  c->lu_valid = false;
-  c->split_of = 0;
-  c->amg_valid = false;
-  c->csr_vals_valid = false;
-  c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
-  // a captured matrix-free application holds the operator's scalar arguments (dt, valency, ...) by
-  // value, which the graph key does not see
-  if (c->mf_opt) c->graphs_clear();
-  // SELL padding slots point at the row itself and are never written by the assembly, so they
-  // must hold zeros in the k-form layout of THIS operator (the SpMV multiplies them)
-  c->vals_const_valid = false;
-  CK(hipMemsetAsync(c->vals.p, 0, sizeof(double) * size_t(c->L.nslots) * c->nks, c->stream),
-     "clear matrix");
+  int rc;
+  if ((rc = c->op_activate(kind, a->dt, a->z))) return rc;
   const pnp::Mesh &m = c->mesh;
   const pnp::LocalLayout &L = c->L;
   int nf = c->nf;
@@ -2662,31 +2689,12 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
       for (int f = 0; f < nf; f++)
         lload[size_t(i) * nf + f] += a->c_extra[size_t(f) * m.nv + L.l2g[i]];
   CK(hipMemcpy(c->dmask.p, lmask.data(), lmask.size(), hipMemcpyHostToDevice), "dmask");
-  {  // the P1 assembly's flag byte per row: its mask bits, and whether its load is to be read --
-     // any entry that is not bitwise +0.0 (-0.0 too); implicit Euler: every row, the device mass
-     // kernel rewrites cvec below
-    std::vector<uint8_t> flag(c->rowflag.n, 0);
-    for (int i = 0; i < L.n_owned; i++) {
-      unsigned fl = ie ? pnp::kRowFlagLoad : 0;
-      for (int f = 0; f < nf; f++) {
-        if (lmask[size_t(i) * nf + f]) fl |= 1u << f;
-        uint64_t bits;
-        std::memcpy(&bits, &lload[size_t(i) * nf + f], sizeof bits);
-        if (bits) fl |= pnp::kRowFlagLoad;
-        if (a->c_extra) {  // a caller's entry flags its row whatever the sum came to (-0.0 too)
-          std::memcpy(&bits, &a->c_extra[size_t(f) * m.nv + L.l2g[i]], sizeof bits);
-          if (bits) fl |= pnp::kRowFlagLoad;
-        }
-      }
-      flag[i] = uint8_t(fl);
-    }
+  {  // (implicit Euler: every row's load is read, the device mass kernel rewrites cvec below)
+    const std::vector<uint8_t> flag = c->row_flags(nf, ie, lmask, lload, a->c_extra);
     CK(hipMemcpy(c->rowflag.p, flag.data(), flag.size(), hipMemcpyHostToDevice), "row flags");
     c->hrowflag.assign(flag.begin(), flag.begin() + L.n_owned);
   }
   // the reference-order mode's copies (external layout, global vertex order)
-  c->seq_op_valid = false;
-  c->seq_dt = a->dt;
-  c->seq_z = a->z;
   c->seq_cextra = a->c_extra != nullptr;
   c->seq_mask_h.assign(size_t(nf) * m.nv, 0);
   if (c->degree == 1)
@@ -2700,7 +2708,6 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
   hcopy(kind == PNP_OP_POISSON ? a->cp : nullptr, m.nv, c->seq_cp_h);
   hcopy(kind == PNP_OP_POISSON ? a->cm : nullptr, m.nv, c->seq_cm_h);
   hcopy(ie ? a->x_old : nullptr, size_t(nf) * m.nv, c->seq_xold_h);
-  c->dl.dmask = c->dmask.p;
   c->hmask = lmask;
   CK(hipMemcpy(c->cvec.p, lload.data(), sizeof(double) * lload.size(), hipMemcpyHostToDevice),
      "cvec");
@@ -2711,7 +2718,6 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
     hipError_t e = hipMemcpy(d, tmp.data(), sizeof(double) * nloc, hipMemcpyHostToDevice);
     return e == hipSuccess ? PNP_OK : c->hipfail(e, "aux upload");
   };
-  int rc;
   if (kind == PNP_OP_DIFF || kind == PNP_OP_DIFF_IMPLICIT_EULER)
     if ((rc = up_field(a->phi, c->aux0.p))) return rc;
   if (kind == PNP_OP_POISSON)
@@ -2727,36 +2733,27 @@ extern "C" int pnp_set_operator(pnp_ctx *c, const pnp_op_args *a) {
          "mass apply");
     CK(hipStreamSynchronize(c->stream), "mass apply");
   }
-  pnp::AsmArgs &aa = c->aa;
-  aa = pnp::AsmArgs{};
-  aa.kind = kind;  // PNP_OP_* == pnp::OP_* by construction
-  aa.l_b = c->params.l_b;
-  aa.c0 = c->params.c0;
-  aa.tau = c->params.tau;
-  aa.pi = c->params.pi;
-  aa.dt = a->dt;
-  aa.z = a->z;
-  aa.cylindrical = c->params.cylindrical;
-  aa.aux0 = c->aux0.p;
-  aa.aux1 = c->aux1.p;
-  aa.cvec = c->cvec.p;
-  aa.dmask = c->dmask.p;
-  aa.rowflag = c->rowflag.p;
-  aa.vals = c->vals.p;
   return PNP_OK;
 }
 
-// reference-order mode: x / r external layout, host or device
+// reference-order mode: an external-layout vector of the caller's (host, or dev: device) into /
+// out of one of the mode's device vectors, on the stream
+static hipError_t seq_in(pnp_ctx *c, double *dst, const double *src, bool dev) {
+  return hipMemcpyAsync(dst, src, 8 * size_t(c->nseq()),
+                        dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream);
+}
+static hipError_t seq_out(pnp_ctx *c, double *dst, const double *src, bool dev) {
+  return hipMemcpyAsync(dst, src, 8 * size_t(c->nseq()),
+                        dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream);
+}
+
 static int seq_residual_abi(pnp_ctx *c, const double *x, double *r, bool dev) {
   int rc;
   if ((rc = c->seq_build())) return rc;
-  const size_t n = c->nseq();
   double *sx = c->sq(pnp_ctx::SQ_X), *sr = c->sq(pnp_ctx::SQ_R);
-  CK(hipMemcpyAsync(sx, x, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
-     "seq upload");
+  CK(seq_in(c, sx, x, dev), "seq upload");
   if ((rc = c->seq_residual(sx, sr))) return rc;
-  CK(hipMemcpyAsync(r, sr, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream),
-     "seq download");
+  CK(seq_out(c, r, sr, dev), "seq download");
   CK(hipStreamSynchronize(c->stream), "seq residual");
   return PNP_OK;
 }
@@ -2764,36 +2761,17 @@ static int seq_jacobian_abi(pnp_ctx *c, const double *x, bool dev, bool fd) {
   int rc;
   if ((rc = c->seq_build())) return rc;
   double *sx = c->sq(pnp_ctx::SQ_X);
-  CK(hipMemcpyAsync(sx, x, 8 * size_t(c->nseq()),
-                    dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
-     "seq upload");
+  CK(seq_in(c, sx, x, dev), "seq upload");
   if ((rc = c->seq_jacobian(sx, fd))) return rc;
   CK(hipStreamSynchronize(c->stream), "seq jacobian");
   return PNP_OK;
 }
 
 extern "C" int pnp_residual(pnp_ctx *c, const double *x, double *r) {
-  if (!c || !x || !r) return PNP_E_ARG;
-  if (c->kind < 0) return c->fail(PNP_E_STATE, "no operator set");
-  hipSetDevice(c->device);
-  if (c->seq_on()) return seq_residual_abi(c, x, r, false);
-  int rc;
-  if ((rc = c->upload_ext(x, c->nf, c->x.p, true))) return rc;
-  if ((rc = c->assemble(c->x.p, 0))) return rc;
-  return c->download_ext(c->r.p, c->nf, r);
+  return pnp_residual_ex(c, x, r, 0);
 }
 
-extern "C" int pnp_jacobian(pnp_ctx *c, const double *x) {
-  if (!c || !x) return PNP_E_ARG;
-  if (c->kind < 0) return c->fail(PNP_E_STATE, "no operator set");
-  hipSetDevice(c->device);
-  if (c->seq_on()) return seq_jacobian_abi(c, x, false, c->fd_opt != 0);
-  int rc;
-  if ((rc = c->upload_ext(x, c->nf, c->x.p, true))) return rc;
-  if ((rc = c->assemble(c->x.p, 1))) return rc;
-  CK(hipStreamSynchronize(c->stream), "jacobian");
-  return PNP_OK;
-}
+extern "C" int pnp_jacobian(pnp_ctx *c, const double *x) { return pnp_jacobian_ex(c, x, 0); }
 
 extern "C" int pnp_jacobian_export(pnp_ctx *c, int64_t *nnz, int32_t *rowptr, int32_t *col,
                                    double *val) {
@@ -2921,14 +2899,12 @@ extern "C" int pnp_jacobian_apply(pnp_ctx *c, const double *x, const double *z, 
     return c->fail(PNP_E_STATE, "no Jacobian assembled (pass x)");
   }
   if (c->seq_on()) {  // y = A z in BCRSMatrix::mv's order on the CSR view
-    const size_t n = c->nseq();
     double *sz = c->sq(pnp_ctx::SQ_Z), *sy = c->sq(pnp_ctx::SQ_Y);
-    CK(hipMemcpyAsync(sz, z, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
-       "seq upload");
-    CK(pnp::launch_seq_spmv(int(n), c->csr_rowptr.p, c->csr_col.p, c->csr_val.p, sz, sy, c->stream),
+    CK(seq_in(c, sz, z, dev), "seq upload");
+    CK(pnp::launch_seq_spmv(c->nseq(), c->csr_rowptr.p, c->csr_col.p, c->csr_val.p, sz, sy,
+                            c->stream),
        "seq apply");
-    CK(hipMemcpyAsync(y, sy, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream),
-       "seq download");
+    CK(seq_out(c, y, sy, dev), "seq download");
     CK(hipStreamSynchronize(c->stream), "seq apply");
     return PNP_OK;
   }
@@ -2948,12 +2924,10 @@ static int seq_solve_abi(pnp_ctx *c, const double *rhs, double *z, const pnp_sol
   if ((rc = c->seq_build())) return rc;
   const size_t n = c->nseq();
   double *sb = c->sq(pnp_ctx::SQ_B), *sz = c->sq(pnp_ctx::SQ_Z);
-  CK(hipMemcpyAsync(sb, rhs, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream),
-     "seq upload");
+  CK(seq_in(c, sb, rhs, dev), "seq upload");
   CK(hipMemsetAsync(sz, 0, 8 * n, c->stream), "seq upload");
   if ((rc = c->seq_krylov(o, sz, sb, res))) return rc;
-  CK(hipMemcpyAsync(z, sz, 8 * n, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream),
-     "seq download");
+  CK(seq_out(c, z, sz, dev), "seq download");
   CK(hipStreamSynchronize(c->stream), "seq solve");
   return res.breakdown ? PNP_E_BREAKDOWN : PNP_OK;
 }
@@ -3000,15 +2974,7 @@ extern "C" int pnp_jacobian_csr_device(pnp_ctx *c, pnp_csr_view *out) {
 // ---------------------------------------------------------------------------------------------
 extern "C" int pnp_linear_solve(pnp_ctx *c, const double *rhs, double *z, const pnp_solve_opts *o,
                                 pnp_solve_result *res) {
-  if (!c || !rhs || !z || !o || !res) return PNP_E_ARG;
-  hipSetDevice(c->device);
-  std::memset(res, 0, sizeof *res);
-  if (c->seq_on()) return seq_solve_abi(c, rhs, z, *o, *res, false);
-  int rc;
-  if ((rc = c->upload_ext(rhs, c->nf, c->b.p, false))) return rc;
-  if ((rc = c->krylov(c->b.p, c->z.p, *o, *res))) return rc;
-  if ((rc = c->download_ext(c->z.p, c->nf, z))) return rc;
-  return res->breakdown ? PNP_E_BREAKDOWN : PNP_OK;
+  return pnp_linear_solve_ex(c, rhs, z, o, res, 0);
 }
 
 extern "C" int pnp_prec_apply(pnp_ctx *c, int32_t prec, const double *d, double *v) {
@@ -3021,11 +2987,11 @@ extern "C" int pnp_prec_apply(pnp_ctx *c, int32_t prec, const double *d, double 
       return c->fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: preconditioner must be NONE, JACOBI or SSOR_NATURAL");
     const size_t n = c->nseq();
     double *sb = c->sq(pnp_ctx::SQ_B), *sz = c->sq(pnp_ctx::SQ_Z);
-    CK(hipMemcpyAsync(sb, d, 8 * n, hipMemcpyHostToDevice, c->stream), "seq upload");
+    CK(seq_in(c, sb, d, false), "seq upload");
     CK(hipMemsetAsync(sz, 0, 8 * n, c->stream), "seq upload");
     if ((rc = c->seq_prec(prec, sb, sz))) return rc;
     if (prec == PNP_PREC_SSOR_NATURAL && (rc = c->nat_check())) return rc;
-    CK(hipMemcpyAsync(v, sz, 8 * n, hipMemcpyDeviceToHost, c->stream), "seq download");
+    CK(seq_out(c, v, sz, false), "seq download");
     CK(hipStreamSynchronize(c->stream), "seq prec");
     return PNP_OK;
   }
@@ -3039,12 +3005,13 @@ extern "C" int pnp_prec_apply(pnp_ctx *c, int32_t prec, const double *d, double 
 // on_set runs with the accepted value before it is stored; an error from it leaves the option as
 // it was
 static int opt_ilu_f32(pnp_ctx *c, int old, int now) {
-  if (old != now && c->split_of == 2) c->split_of = 0;  // re-split the factors in the new precision
+  // not ilu_factors_drop(): the precision is that of the split copy alone, the fp64 factors in lu
+  // survive and split(2) converts them again (the fused path, which keeps none, refactorises)
+  if (old != now && c->split_of == 2) c->split_of = 0;
   return PNP_OK;
 }
 static int opt_ilu_fused(pnp_ctx *c, int, int) {
-  c->lu_valid = false;
-  if (c->split_of == 2) c->split_of = 0;
+  c->ilu_factors_drop();
   return PNP_OK;
 }
 static int opt_gmres_restart(pnp_ctx *c, int old, int now) {
@@ -3062,11 +3029,7 @@ static int opt_idr_s(pnp_ctx *c, int old, int now) {
 static int opt_seq_order(pnp_ctx *c, int old, int now) {
   if (now && (c->degree > 1 || c->dist))
     return c->fail(PNP_E_ARG, "PNP_OPT_SEQ_ORDER: P1 contexts of one rank only");
-  if (old != now) {
-    c->assembled = false;  // the next Jacobian is assembled in the newly selected form
-    c->csr_vals_valid = false;
-    c->mf_lin = c->vals_stale = c->mf_diag_valid = false;
-  }
+  if (old != now) c->jacobian_drop();  // the next Jacobian is assembled in the newly selected form
   return PNP_OK;
 }
 static int opt_matrix_free(pnp_ctx *c, int, int now) {
@@ -3075,10 +3038,8 @@ static int opt_matrix_free(pnp_ctx *c, int, int now) {
                    "PNP_OPT_MATRIX_FREE: P1 contexts only (the matrix-free application walks the "
                    "P1 vertex fans; P_k contexts assemble)");
   if (!now && c->mf_lin) {
-    // the current Jacobian goes on as an assembled one: its values, if nobody needed them yet
     hipSetDevice(c->device);
-    if (int rc = c->ensure_values()) return rc;
-    c->mf_lin = c->mf_diag_valid = false;
+    if (int rc = c->mf_settle()) return rc;
   }
   // the graphs_clear() at the top of pnp_set_option has dropped every captured BiCGSTAB graph
   // and bumped graph_epoch: no graph captured in one form survives into the other, and none
@@ -3222,7 +3183,7 @@ extern "C" int pnp_amg_configure(pnp_ctx *c, const pnp_amg_opts *o) {
                        o->max_levels != c->amg_opts.max_levels;
   c->amg_opts = *o;
   if (rebuild) c->amg_built = false;
-  c->amg_valid = false;
+  c->amg_values_drop();
   return PNP_OK;
 }
 
@@ -3434,8 +3395,7 @@ extern "C" int pnp_newton(pnp_ctx *c, double *u, const pnp_newton_opts *o, pnp_n
     ~IluRestore() {
       if (saved < 0) return;
       c->ilu_f32 = saved;
-      if (c->split_of == 2) c->split_of = 0;
-      c->lu_valid = false;
+      c->ilu_factors_drop();
     }
   } ilu_restore{c, ilu_saved};
   if ((rc = c->upload_ext(u, c->nf, c->x.p, true))) return rc;
@@ -3494,8 +3454,7 @@ extern "C" int pnp_newton(pnp_ctx *c, double *u, const pnp_newton_opts *o, pnp_n
       // SeqILU0) and keep them for the rest of this call
       if (ilu_saved < 0) ilu_saved = c->ilu_f32;
       c->ilu_f32 = 0;
-      if (c->split_of == 2) c->split_of = 0;
-      c->lu_valid = false;
+      c->ilu_factors_drop();
       CK(hipMemcpyAsync(c->b.p, c->r.p, sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream),
          "rhs");
       if ((rc = c->krylov(c->b.p, c->z.p, lo, sr))) return rc;

@@ -138,14 +138,102 @@ struct pnp_ctx {
   int kind = -1, nf = 0, pat = 0, nvb = 0, nks = 0;  // nvb: block pattern size, nks: stored
   std::vector<uint8_t> hmask;  // Dirichlet mask of the current operator, owned rows x nf
   pnp::AsmArgs aa{};
+
+  // ---- what the context holds of the current operator's Jacobian --------------
+  // The flags, and the only functions that write them: the transitions below, and for each derived
+  // object the function that computes it.
+  //   assembled       a Jacobian of the current operator is held.  Every reader of the flags down
+  //                   to amg_valid sits behind it.  Set by jacobian_stored / seq_jacobian_stored,
+  //                   cleared by jacobian_drop (and by md_run after a failed solve)
+  //   mf_lin          it is held as a linearisation point (PNP_OPT_MATRIX_FREE): jacobian_stored(mf)
+  //   vals_stale      ... and vals does not hold its values yet: jacobian_stored(mf) sets,
+  //                   ensure_values clears; mf_settle and jacobian_drop clear both
+  //   mf_diag_valid   mf_diag holds its diagonal blocks: jacobi_prepare sets, every transition clears
+  //   csr_vals_valid  csr_val holds it: set by csr_values, and by seq_jacobian_stored (the
+  //                   reference-order Jacobian lives there only); cleared by jacobian_stored,
+  //                   jacobian_drop and a new csr_structure
+  //   lu_valid        lu (fused factorisation: lvals / uvals) holds its ILU(0) factors: ilu_factor
+  //                   sets; derived_drop and ilu_factors_drop clear
+  //   split_of        what lvals / uvals hold of it: 0 nothing, 1 the matrix (SSOR), 2 the factors.
+  //                   split and ilu_factor set; derived_drop clears, ilu_factors_drop clears a 2
+  //   amg_valid       the AMG's coarse values come from it: amg_setup sets; derived_drop and
+  //                   amg_values_drop (pnp_amg_configure) clear
+  // and of the operator itself:
+  //   vals_const_valid  vals holds the PNP k-form's state-independent planes for the operator set
+  //                   now: set by a P1 analytic assembly that wrote every plane (asm_wrote), cleared
+  //                   by whatever else zeroes or writes vals (op_activate, set_fd, the FD and P_k
+  //                   Jacobians, a failed launch).  About the contents of vals, not about a derived
+  //                   object: jacobian_drop leaves it alone
+  //   seq_op_valid    the reference-order copies of the operator are on the device: seq_prepare sets,
+  //                   op_activate clears
+  bool assembled = false, mf_lin = false, vals_stale = false, mf_diag_valid = false;
+  bool csr_vals_valid = false, lu_valid = false, amg_valid = false;
+  int split_of = 0;
+  bool vals_const_valid = false, seq_op_valid = false;
+  // what is computed from the stored Jacobian's values
+  void derived_drop() {
+    lu_valid = false;
+    split_of = 0;
+    amg_valid = false;
+  }
+  void amg_values_drop() { amg_valid = false; }
+  // the factors are recomputed (another factorisation path or precision); a split matrix stays
+  void ilu_factors_drop() {
+    if (split_of == 2) split_of = 0;
+    lu_valid = false;
+  }
+  // assemble() now holds a Jacobian: in vals, or (mf) as a linearisation point
+  void jacobian_stored(bool mf) {
+    assembled = true;
+    derived_drop();
+    csr_vals_valid = false;
+    mf_lin = vals_stale = mf;
+    mf_diag_valid = false;
+  }
+  // seq_jacobian() now holds one, in the CSR view only.  The mf_* flags stay: they describe the
+  // k-form Jacobian pnp_assemble_state may have stored in this mode, which
+  // pnp_bicgstab_iterations goes on applying
+  void seq_jacobian_stored() {
+    assembled = true;
+    derived_drop();
+    csr_vals_valid = true;
+  }
+  // no Jacobian is held: another operator, value layout or arithmetic order comes next
+  void jacobian_drop() {
+    assembled = false;
+    derived_drop();
+    csr_vals_valid = false;
+    mf_lin = vals_stale = mf_diag_valid = false;
+  }
+  // PNP_OPT_MATRIX_FREE off: the current Jacobian goes on as an assembled one -- its values, if
+  // nobody needed them yet
+  int mf_settle() {
+    if (int rc = ensure_values()) return rc;
+    mf_lin = mf_diag_valid = false;
+    return PNP_OK;
+  }
+  // the current operator: fields, block pattern of the analytic Jacobian
+  static int nfields_of(int kind) {
+    return (kind == PNP_OP_PNP || kind == PNP_OP_PNP_IMPLICIT_EULER) ? 3 : 1;
+  }
+  static int base_pat(int kind) {
+    return kind == PNP_OP_PNP ? pnp::kPatPnp
+                              : (kind == PNP_OP_PNP_IMPLICIT_EULER ? pnp::kPatPnpIE : pnp::kPatScalar);
+  }
+  // `kind` becomes the current operator (pnp_set_operator, md_activate; ctx.cc): pattern, no
+  // Jacobian, vals zeroed on the stream, the AsmArgs on the context's operator buffers -- which
+  // the caller fills (mask, row flags, load, frozen fields), with the reference-order copies
+  int op_activate(int kind, double dt, double z);
+  // the P1 assembly's flag byte per owned row, whole SELL chunks (ctx.cc)
+  std::vector<uint8_t> row_flags(int nfk, bool ie, const std::vector<uint8_t> &lmask,
+                                 const std::vector<double> &lload, const double *c_extra) const;
+
   DBuf<double> vals, lu;  // matrix and its ILU(0) factors
-  bool lu_valid = false;
   // triangular split storage (DevLayout l*/u*): lvals/uvals hold either the matrix (SSOR) or the
-  // ILU(0) factors; split_of says which is current (0 none, 1 matrix, 2 factors)
+  // ILU(0) factors; split_of says which is current
   DBuf<int> d_lchunk_len, d_lchunk_off, d_lcolidx, d_lsrc, d_uchunk_len, d_uchunk_off, d_ucolidx,
       d_usrc;
   DBuf<double> lvals, uvals, tsgs;
-  int split_of = 0;
   // ILU(0) factors in the split storage in single precision (PNP_OPT_ILU_F32, default 1; the
   // sweeps compute in fp64, the matrix, SpMV, SSOR and every vector stay fp64).  Measured at
   // config 3: ILU(0) apply 119 -> 95 us, BiCGSTAB 428 -> 389 us/it, Newton 9,295 -> 9,177
@@ -214,7 +302,6 @@ struct pnp_ctx {
   DBuf<int> csr_rowptr, csr_col, csr_src;
   DBuf<unsigned char> csr_vidx;
   DBuf<double> csr_val;
-  bool csr_vals_valid = false;  // csr_val holds the current Jacobian
   // natural-order SSOR (PNP_PREC_SSOR_NATURAL, ssor_natural.hip): level schedules of the forward
   // and backward sweeps over the external-layout rows with each level's rows as an ELL over the
   // CSR (pnp::NatSweep; built with the CSR structure), and external-layout work vectors
@@ -280,7 +367,7 @@ struct pnp_ctx {
   long long ilu_flow_n = 0;    // flow launches issued (pnp_info; a graph capture counts once)
   // ---- reference-order mode (PNP_OPT_SEQ_ORDER, seq_order.hip) -----------------------------
   int seq_opt = 0;
-  bool seq_built = false, seq_op_valid = false;
+  bool seq_built = false;
   DBuf<int> seq_tri, seq_vptr, seq_vinc;
   DBuf<double> seq_xy;
   // the operator's data as the reference holds it: constrained rows (external layout), frozen
@@ -305,36 +392,28 @@ struct pnp_ctx {
   DBuf<uint8_t> rowflag;
   std::vector<uint8_t> hrowflag;  // its owned rows on the host (pnp_asm_row_flags)
   DBuf<double> cvec, aux0, aux1;
-  bool assembled = false;
   bool after_solve = false;  // a linear solve ran since the last Jacobian assembly (AsmArgs::cold)
   // ---- matrix-free Jacobian application (PNP_OPT_MATRIX_FREE, jac_apply.hip) ----
   // With the option on, a Jacobian "assembly" of a P1 analytic operator records the linearisation
   // point (mf_x: the state with ghosts; mf_aa: the operator's arguments at that moment) and leaves
   // the SELL values stale; halo_spmv and pnp_jacobian_apply compute J z from the point, and the
   // consumers of vals (SSOR / ILU(0) / AMG set-up, the CSR view, the export) first run the
-  // ordinary assembly at the point (ensure_values).  mf_lin: the current Jacobian is held this
-  // way; vals_stale: vals does not hold it yet.
+  // ordinary assembly at the point (ensure_values).
   int mf_opt = 0;
-  bool mf_lin = false, vals_stale = false;
   pnp::AsmArgs mf_aa{};
   DBuf<double> mf_x, mf_r;  // the point; the residual ensure_values' fused assembly also writes
   // Jacobi without SELL values: the diagonal blocks alone, one slot per chunk (launch_jac_diag),
   // read by launch_jacobi through a layout whose chunk_off[c] = 64 c
   DBuf<double> mf_diag;
   DBuf<int> mf_choff;
-  bool mf_diag_valid = false;
   long long mf_applies = 0, value_assemblies = 0;  // pnp_matfree_info
   // ---- state-independent planes of the PNP k-form (PNP_OPT_ASM_REUSE_CONST) ----
-  // k0 / k1 of every PNP block depend on the mesh and the parameters only.
-  // vals_const_valid: vals holds them for the operator set now -- set by a P1 analytic assembly
-  // that wrote every plane, cleared by whatever else zeroes or writes vals (pnp_set_operator,
-  // set_fd, the FD and P_k Jacobians).  While it holds, the PNP Jacobian assembly leaves those
-  // planes alone (AsmArgs::kconst).
+  // k0 / k1 of every PNP block depend on the mesh and the parameters only.  While vals_const_valid
+  // holds, the PNP Jacobian assembly leaves those planes alone (AsmArgs::kconst).
   int asm_reuse_opt = [] {  // the environment variable PNP_ASM_REUSE_CONST=0/1 sets the default
     const char *e = std::getenv("PNP_ASM_REUSE_CONST");
     return (e && std::atoi(e) == 0) ? 0 : 1;
   }();
-  bool vals_const_valid = false;
   // pnp_asm_info; asm_piped: launches of the persistent, prefetching walk (PNP_ASM_PIPE)
   long long asm_full = 0, asm_reused = 0, asm_piped = 0;
   // (the variant exists for the gather-all walk only: layouts with a fan of more than 8 neighbours
@@ -369,7 +448,7 @@ struct pnp_ctx {
     return v;
   }
   std::vector<std::unique_ptr<AmgDev>> amg_d;  // amg_d[k] = level k + 1
-  bool amg_built = false, amg_valid = false;
+  bool amg_built = false;
   int amg_nf = 0;
   double amg_setup_ms = 0;
   DBuf<double> amg_ainv, amg_x0, amg_t, amg_y, amg_r, amg_z;

@@ -33,19 +33,8 @@ int pnp_ctx::md_op_build(MdOp &op, int k, int field, double z) {
   op.z = z;
   std::vector<double> lload;
   op_static(k, field, 0.0, op.gmask, op.hmask, lload);
-  // the row flags as pnp_set_operator derives them: the mask bit, and whether the row's load is
-  // read -- every row of an implicit-Euler operator (the mass kernel rewrites cvec), else the
-  // rows whose load is not bitwise +0.0
-  const bool ie = k == PNP_OP_DIFF_IMPLICIT_EULER;
-  op.hflag.assign(rowflag.n, 0);
-  for (int i = 0; i < L.n_owned; i++) {
-    unsigned fl = ie ? pnp::kRowFlagLoad : 0;
-    if (op.hmask[size_t(i)]) fl |= 1u;
-    uint64_t bits;
-    std::memcpy(&bits, &lload[size_t(i)], sizeof bits);
-    if (bits) fl |= pnp::kRowFlagLoad;
-    op.hflag[size_t(i)] = uint8_t(fl);
-  }
+  // (every row of an implicit-Euler operator reads its load: the mass kernel rewrites cvec)
+  op.hflag = row_flags(1, k == PNP_OP_DIFF_IMPLICIT_EULER, op.hmask, lload, nullptr);
   int rc;
   if ((rc = upv(op.mask, op.hmask, "md mask")) || (rc = upv(op.flag, op.hflag, "md row flags")) ||
       (rc = upv(op.load, lload, "md load")))
@@ -53,25 +42,11 @@ int pnp_ctx::md_op_build(MdOp &op, int k, int field, double z) {
   return PNP_OK;
 }
 
-// `op` becomes the context's operator, as pnp_set_operator makes one current: the matrix cleared,
-// every derived object invalid; the mask and flags from the operator's device copies, the frozen
-// fields a0 / a1 (n_local, with ghosts) from the resident state.  cvec is md_cvec's.
+// `op` becomes the context's operator through op_activate, as in pnp_set_operator; the mask and
+// flags from the operator's device copies, the frozen fields a0 / a1 (n_local, with ghosts) from
+// the resident state.  cvec is md_cvec's.
 int pnp_ctx::md_activate(const MdOp &op, double dt, const double *a0, const double *a1) {
-  kind = op.kind;
-  fd_mode = false;
-  nf = 1;
-  pat = pnp::kPatScalar;
-  nvb = pnp::popc9(pat);
-  nks = pnp::nks_of(pat);
-  assembled = false;
-  lu_valid = false;
-  split_of = 0;
-  amg_valid = false;
-  csr_vals_valid = false;
-  mf_lin = vals_stale = mf_diag_valid = false;
-  if (mf_opt) graphs_clear();
-  vals_const_valid = false;
-  CKH(hipMemsetAsync(vals.p, 0, sizeof(double) * size_t(L.nslots) * nks, stream), "clear matrix");
+  if (int rc = op_activate(op.kind, dt, op.z)) return rc;
   if (L.n_owned)
     CKH(hipMemcpyAsync(dmask.p, op.mask.p, size_t(L.n_owned), hipMemcpyDeviceToDevice, stream),
         "md mask");
@@ -79,11 +54,7 @@ int pnp_ctx::md_activate(const MdOp &op, double dt, const double *a0, const doub
       "md row flags");
   hrowflag.assign(op.hflag.begin(), op.hflag.begin() + L.n_owned);
   hmask = op.hmask;
-  dl.dmask = dmask.p;
   // reference-order mode is refused by pnp_md_run; its copies are those of no operator
-  seq_op_valid = false;
-  seq_dt = dt;
-  seq_z = op.z;
   seq_cextra = false;
   seq_mask_h.assign(size_t(mesh.nv), 0);
   seq_phi_h.clear();
@@ -93,21 +64,6 @@ int pnp_ctx::md_activate(const MdOp &op, double dt, const double *a0, const doub
   const size_t nlb = sizeof(double) * size_t(L.n_owned + L.n_ghost);
   if (a0) CKH(hipMemcpyAsync(aux0.p, a0, nlb, hipMemcpyDeviceToDevice, stream), "md aux");
   if (a1) CKH(hipMemcpyAsync(aux1.p, a1, nlb, hipMemcpyDeviceToDevice, stream), "md aux");
-  aa = pnp::AsmArgs{};
-  aa.kind = op.kind;
-  aa.l_b = params.l_b;
-  aa.c0 = params.c0;
-  aa.tau = params.tau;
-  aa.pi = params.pi;
-  aa.dt = dt;
-  aa.z = op.z;
-  aa.cylindrical = params.cylindrical;
-  aa.aux0 = aux0.p;
-  aa.aux1 = aux1.p;
-  aa.cvec = cvec.p;
-  aa.dmask = dmask.p;
-  aa.rowflag = rowflag.p;
-  aa.vals = vals.p;
   return PNP_OK;
 }
 

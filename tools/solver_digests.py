@@ -1,5 +1,5 @@
-"""Every linear solver x preconditioner and two Newton runs on small systems: iteration counts and
-solution digests, one JSON line each (PNP_AMD_LIB selects the library)."""
+"""Every linear solver x preconditioner, two Newton runs and the device md loop on small systems:
+iteration counts and solution digests, one JSON line each (PNP_AMD_LIB selects the library)."""
 import hashlib
 import json
 import os
@@ -68,4 +68,23 @@ ctx.set_operator(P.OP_PNP)
 u, nres = ctx.newton(x3, prec=P.PREC_ILU0, maxit=10)
 out(op="pnp", newton=nres["iterations"], linear=nres["linear_iterations"], conv=nres["converged"],
     sol=h(u))
+ctx.close()
+
+# the operator-split time loop on the device: pore_pnp unrefined, 3 steps from the Boltzmann state
+cfg = P.read_config(os.path.join(ROOT, "data", "pore_pnp", "pore.cfg"))
+mesh = P.Mesh.read_gmsh(cfg.meshfile)
+s = cfg.system
+ctx = P.Context(mesh, P.Params.from_config(cfg))
+ctx.set_operator(P.OP_PB)
+phi, _ = ctx.newton(np.zeros(mesh.nv), reduction=1e-9, prec=P.PREC_SSOR)
+u0 = ctx.initial_state(phi)
+for pname, prec in (("amg_ssor", P.PREC_AMG), ("ssor", P.PREC_SSOR)):
+    if prec == P.PREC_AMG:
+        ctx.amg_configure(smoother=P.PREC_SSOR)
+    for reuse in (0, 1):
+        # dt well under the charge relaxation time 1 / (8 pi l_b c0): every solve converges
+        u, t, ip, im, res = ctx.md_run(u0, 0.05, 3, max(1, s["potentialUpdateFreq"]),
+                                       max(1, s["outputFreq"]), prec=prec, reuse=reuse)
+        res.pop("elapsed")
+        out(op="md", prec=pname, reuse=reuse, state=h(u), t=h(t), ip=h(ip), im=h(im), **res)
 ctx.close()
