@@ -14,6 +14,7 @@ import scipy.sparse as sp
 import meshio
 import oracle_py as O
 import pnp_amd as P
+from amg_ref import PATS, ilu0_dense as _ilu0_dense
 from conftest import DATA
 
 pytestmark = pytest.mark.gpu
@@ -387,25 +388,6 @@ def test_cpp_driver_reference_solvers(tmp_path):
 
 
 # ---- multicolour ILU(0) --------------------------------------------------------------------------
-# stored block patterns (dune-pnp_amd/csrc/kernels.h kPatPnp / kPatPnpIE): PnpOperator has no
-# c+/c- coupling; PnpTOperator's c- mass term lands in the c+ rows (quirk Q2) -> (1,2) present
-PATS = {"pnp": [(f, g) for f in range(3) for g in range(3) if (f, g) not in ((1, 2), (2, 1))],
-        "pnp_ie": [(f, g) for f in range(3) for g in range(3) if (f, g) != (2, 1)],
-        "pb": [(0, 0)]}
-
-
-def _ilu0_dense(A, M):
-    """Textbook IKJ ILU(0) restricted to the pattern M (Saad, Alg. 10.4); pivots not inverted."""
-    A = A.copy()
-    n = A.shape[0]
-    for i in range(n):
-        for k in np.nonzero(M[i, :i])[0]:
-            A[i, k] /= A[k, k]
-            q = np.nonzero(M[i, k + 1:] & M[k, k + 1:])[0] + k + 1
-            A[i, q] -= A[i, k] * A[k, q]
-    return A
-
-
 @pytest.mark.parametrize("f32", [0, 1, 2, 3])
 @pytest.mark.parametrize("name,kind", [("pore_small_k0", "pnp"), ("pore_small_k0", "pnp_ie"),
                                        ("pore_small_k0", "pb"), ("cylinder_k0", "pnp")])

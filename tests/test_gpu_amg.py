@@ -13,10 +13,10 @@ import os
 
 import numpy as np
 import pytest
-import scipy.sparse as sp
 import scipy.sparse.linalg as spla
 
 import pnp_amd as P
+from amg_ref import interleave, numpy_vcycle
 from conftest import DATA
 
 pytestmark = pytest.mark.gpu
@@ -27,68 +27,6 @@ def problem(cfgname, k):
     mesh = P.Mesh.load(cfg.meshfile).refine(k)
     par = P.Params.from_config(cfg)
     return mesh, par
-
-
-def interleave(A, nv, nf):
-    perm = np.array([f * nv + v for v in range(nv) for f in range(nf)])
-    return A[perm][:, perm].tocsr(), perm
-
-
-def numpy_vcycle(A0, nf, aggs, omega, d, sweeps=2, pre0=True, f32=True):
-    """The V-cycle of amg.hip restated: Jacobi (pointwise) smoothing on level 0, `sweeps` damped
-    block-Jacobi sweeps before and after the correction on the coarse levels, exact solve on the
-    coarsest.  f32 (PNP_AMG_F32, the default): the coarse levels' sweeps and residuals multiply by
-    the block values rounded to single precision, the coarsest solve by the inverse rounded to
-    single precision; the Galerkin products and the diagonal inverses use the fp64 values."""
-    As, Ps = [A0], []
-    for agg in aggs:
-        n = As[-1].shape[0] // nf
-        Pv = sp.csr_matrix((np.ones(n), (np.arange(n), agg)), shape=(n, int(agg.max()) + 1))
-        Pm = sp.kron(Pv, sp.identity(nf), format="csr")
-        Ps.append(Pm)
-        As.append((Pm.T @ As[-1] @ Pm).tocsr())
-    K = len(aggs)
-    Ad = As  # fp64: Galerkin (above), diagonal inverses, coarsest solve
-    if f32:
-        As = [A if k in (0, K) else sp.csr_matrix(
-            (A.data.astype(np.float32).astype(np.float64), A.indices, A.indptr), shape=A.shape)
-            for k, A in enumerate(Ad)]
-
-    def dinv(A):
-        nb = A.shape[0] // nf
-        D = np.zeros((nb, nf, nf))
-        C = A.tocoo()
-        m = (C.row // nf) == (C.col // nf)
-        np.add.at(D, (C.row[m] // nf, C.row[m] % nf, C.col[m] % nf), C.data[m])
-        return np.linalg.inv(D)
-
-    def bj(A, Di, r):
-        return np.einsum("bij,bj->bi", Di, r.reshape(-1, nf)).ravel()
-
-    Dis = [None] + [dinv(Ad[k]) for k in range(1, K)]
-    diag0 = A0.diagonal()
-    x0 = d / diag0 if pre0 else np.zeros_like(d)
-    b, x = [None] * (K + 1), [None] * (K + 1)
-    b[1] = Ps[0].T @ (d - A0 @ x0)
-    if K > 1:
-        x[1] = omega * bj(As[1], Dis[1], b[1])
-    for k in range(1, K):
-        for _ in range(sweeps - 1):
-            x[k] = x[k] + omega * bj(As[k], Dis[k], b[k] - As[k] @ x[k])
-        b[k + 1] = Ps[k].T @ (b[k] - As[k] @ x[k])
-        if k + 1 < K:
-            x[k + 1] = omega * bj(As[k + 1], Dis[k + 1], b[k + 1])
-    if f32:
-        e = np.linalg.inv(Ad[K].toarray()).astype(np.float32).astype(np.float64) @ b[K]
-    else:
-        e = np.linalg.solve(Ad[K].toarray(), b[K])
-    for k in range(K - 1, 0, -1):
-        xc = x[k] + Ps[k] @ e
-        e = xc + omega * bj(As[k], Dis[k], b[k] - As[k] @ xc)
-        for _ in range(sweeps - 1):
-            e = e + omega * bj(As[k], Dis[k], b[k] - As[k] @ e)
-    y = x0 + Ps[0] @ e
-    return y + (d - A0 @ y) / diag0
 
 
 @pytest.mark.parametrize("kind,sweeps,pre0", [("pb", 1, 1), ("pb", 2, 1), ("pnp", 1, 1),
