@@ -280,8 +280,27 @@ __device__ __forceinline__ int const_ld(const int *p, int i) {
 __device__ __forceinline__ int row_block_const(const DevLayout &L, int b, int nwg) {  // row_block
   return L.blkmap ? const_ld(L.blkmap, xcd_block(b, nwg, 1)) : xcd_block(b, nwg, L.xcd_remap);
 }
+// REG (PNP_ASM_REGULAR=1, the default; OP_PNP, the direct constant-planes Jacobian walk): a wave
+// whose live rows are all closed six-neighbour fans without a break (rowmeta: len 7, closed, no
+// break bit -- a wave vote, so the branch is scalar) walks its six elements (i,v1,v2) .. (i,v5,v6),
+// (i,v6,v1) with static slots: no s < len / has_next / closed / brk tests and no wrap selects, 6
+// index loads and 6 gathers instead of 8 and 8 (slots 7 and 8 of such a row re-read the row
+// itself).  All of them and the flag byte are issued before the first store, so no later wait
+// drains the block stores, and a wave without a flagged row ends without waiting for them.  The
+// geometry() / element() calls, their operands and their order, the F / P / D handling and the
+// store order are the general walk's for such a row, and the fp64 instruction multiset is that of
+// the general walk unrolled for six neighbours (tools/isa_regs.py with -DASM_REGULAR_CHECK) plus
+// the adds of a second residual tail: the same bits.  Every other wave falls through to the
+// general walk below.  160 VGPRs, no spill.  The full-write instantiation (KC = 0, once per
+// operator) has ten more accumulator registers live and spills with it (11 VGPRs): it keeps the
+// general walk for every wave.
+template <int OP>
+constexpr int asm_reg() {  // 1: the operator has the regular walk
+  return OP == OP_PNP;
+}
+constexpr int kRegSlots = 7;  // slots of a regular row: the diagonal and six neighbours
 template <int OP, int JAC, int MINW, int FANR, int SPLIT = FANR, int STAGE = 0, int LDSG = 0,
-          int KC = 0, int PIPE = 0>
+          int KC = 0, int PIPE = 0, int REG = 0>
 __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs a) {
   using T = OpTraits<OP>;
   constexpr int NF = T::NF, NK = T::NK, NS = FANR;
@@ -289,6 +308,8 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
   constexpr bool AUX1 = OP == OP_POISSON;
   constexpr int RW = asm_lds_rec<OP>();
   static_assert(!PIPE || (JAC && FANR == 9 && !STAGE && !LDSG), "PIPE: the direct Jacobian walk");
+  static_assert(!REG || (OP == OP_PNP && JAC && KC && FANR == 9 && !STAGE && !LDSG && !PIPE),
+                "REG: OP_PNP, the direct constant-planes Jacobian walk");
   extern __shared__ double srec[];  // LDSG: [cnt][RW] = x, y, dofs, aux0, aux1
   __shared__ uint32_t pfb[PIPE ? 4 * kPipeDw * kRows : 1];  // PIPE: the waves' prefetch regions
   // PIPE, wave-uniform: the 256-row blocks of this and the next two tiles (-1: none), this and
@@ -349,6 +370,105 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
     // neighbour records, instead of after its barrier)
     const int row = live ? row0 : 0;
     const int chunk = row / kRows, lane = row % kRows;
+    if constexpr (REG) {
+      const uint64_t meta = L.rowmeta[row];
+      const bool regular =
+          int(meta & 63) == kRegSlots && ((meta >> 6) & 1) && (meta >> 8) == 0;
+      if (__all(regular)) {  // dead lanes have returned: a vote of the live rows
+        // every row of the chunk has its seven slots: no bound on the index loads
+        const int off = L.chunk_off[chunk];
+        const int *__restrict__ cix = L.colidx + off + lane;
+        int cr[kRegSlots];
+#pragma unroll
+        for (int k = 1; k < kRegSlots; k++) cr[k] = cix[k * kRows];
+        const unsigned fl = a.rowflag[row];
+        const double2 pi2 = reinterpret_cast<const double2 *>(L.xy)[row];
+        double ui[NF];
+        load_nf<NF>(a.x, size_t(row), ui);
+        double2 pn[kRegSlots];
+        double un[kRegSlots][NF];
+        auto gather = [&](int k) {
+          pn[k] = reinterpret_cast<const double2 *>(L.xy)[cr[k]];
+          load_nf<NF>(a.x, size_t(cr[k]), un[k]);
+        };
+        // slot 6 is gathered in element 2, just ahead of the first store, when element 2's
+        // temporaries are dead: with all six up front, or slot 6 before element 2, the kernel spills
+#pragma unroll
+        for (int k = 1; k < kRegSlots - 1; k++) gather(k);
+        double *__restrict__ vc = a.vals + size_t(off) * NK;
+        double R[NF], D[NK], P[NK], F[NK];
+#pragma unroll
+        for (int f = 0; f < NF; f++) R[f] = 0;
+#pragma unroll
+        for (int v = 0; v < NK; v++) D[v] = P[v] = F[v] = 0;
+#pragma unroll
+        for (int s = 1; s < kRegSlots; s++) {
+          const int t = s + 1 < kRegSlots ? s + 1 : 1;  // static: the fan wraps after slot 6
+          // Each element works on copies of its two neighbours that went through an empty asm,
+          // v_t's first, then v_s's.  The copies make every element's arithmetic independent of
+          // its neighbours', as in the general walk, where v_t comes through a per-lane select:
+          // otherwise the compiler shares y_c / 120 and (y_i + y_c) / 60 with the next element's
+          // y_b terms, and a product with a second use is fused the other way round.  The order
+          // makes v_t's values the older ones, as the general walk's statements do: the compiler
+          // orders the two products of Mib and Mic by the age of their inputs and fuses the first.
+          // Either way Mib and Mic, and with them one residual entry in a hundred, came out an ulp
+          // off the general walk's.
+          double2 pt = pn[t], ps = pn[s];
+          double ut[NF], us[NF];
+          asm volatile("" : "+v"(pt.x), "+v"(pt.y));
+#pragma unroll
+          for (int f = 0; f < NF; f++) {
+            ut[f] = un[t][f];
+            asm volatile("" : "+v"(ut[f]));
+          }
+          asm volatile("" : "+v"(ps.x), "+v"(ps.y));
+#pragma unroll
+          for (int f = 0; f < NF; f++) {
+            us[f] = un[s][f];
+            asm volatile("" : "+v"(us[f]));
+          }
+          Geo G;
+          geometry(pi2.x, pi2.y, ps.x, ps.y, pt.x, pt.y, G);
+          double Ct[NK];
+#pragma unroll
+          for (int v = 0; v < NK; v++) Ct[v] = 0;
+          element<OP, JAC, KC>(a, G, pi2.y, ps.y, pt.y, ui, us, ut, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, R,
+                               D, P, Ct);
+          if (s == 1) {
+#pragma unroll
+            for (int v = 0; v < NK; v++) F[v] = P[v];
+          } else {
+            if (s == 2) gather(kRegSlots - 1);
+            store_block<OP, KC>(vc, lane, s, P);
+          }
+#pragma unroll
+          for (int v = 0; v < NK; v++) P[v] = Ct[v];
+          // R and D are read only after the last element, and without the general walk's
+          // branches the compiler sinks all six elements' contributions to them down there,
+          // keeping every element's geometry alive (59 VGPRs spilled); an empty asm that names
+          // the running sums keeps each addition in its element
+#pragma unroll
+          for (int f = 0; f < NF; f++) asm volatile("" : "+v"(R[f]));
+#pragma unroll
+          for (int v = 2; v < NK; v++) asm volatile("" : "+v"(D[v]));  // KC: k2 ..
+        }
+#pragma unroll
+        for (int v = 0; v < NK; v++) F[v] += P[v];
+        store_block<OP, KC>(vc, lane, 1, F);
+        store_block<OP, KC>(vc, lane, 0, D);
+        // Only a wave with a flagged row reads cvec.  The others get a tail of their own with no
+        // load in it, hence no wait at its top for the wave's block stores (the compiler waits
+        // vmcnt(0) where the two paths of the per-lane load join).
+        if (__any(fl & kRowFlagLoad))
+          residual_tail<NF>(a, row, fl, R);
+        else
+          residual_tail<NF>(a, row, fl & ~unsigned(kRowFlagLoad), R);
+        return;
+      }
+#ifdef ASM_REGULAR_CHECK  // ISA check build: the regular walk alone (tools/isa_regs.py)
+      return;
+#endif
+    }
     int cj[NS];  // the fan's columns (LDSG: their positions in the staged list)
     uint64_t meta_pf = 0;
     unsigned fl_pf = 0;
@@ -555,6 +675,12 @@ __global__ __launch_bounds__(256, MINW) void k_assemble_ga(DevLayout L, AsmArgs 
   } while (PIPE && advance());
 }
 
+#ifdef ASM_REGULAR_CHECK
+// ISA check build: the general walk unrolled for six neighbours, whose fp64 instruction multiset
+// the regular walk (alone in its kernels under this flag) must show
+template __global__ void k_assemble_ga<OP_PNP, 1, 3, 7, 7, 0, 0, 1>(DevLayout, AsmArgs);
+#endif
+
 // cvec[row] -= M(x_old)[row]: PnpTOperator (tau * (c+ + c-) into the c+ row, Q2) or the
 // DiffusionTOperator mass, for the implicit Euler residual M(u) - M(u_old) + dt R(u).
 template <int OP>
@@ -656,6 +782,8 @@ hipError_t launch_ion_flux(int ns, const int4 *seg, const double *xy, const doub
 // against 39.6 for the direct walk (parent commit: 42.4), at every grid from one tile per
 // workgroup to the resident grid (profiles/asm_pipe/)
 constexpr bool kAsmPipeDefault = false;
+// PNP_ASM_REGULAR's default (profiles/asm_regular/)
+constexpr bool kAsmRegularDefault = true;
 
 // The pipelined walk's launch (operators with constant planes: OP_PNP).  Grid: the workgroups
 // resident at once (occupancy x CUs) rounded down to a multiple of 8, at most one per tile, at
@@ -751,6 +879,12 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
     const char *e = getenv("PNP_ASM_PIPE_GRID");
     return (e && atoi(e) >= 1) ? atoi(e) : 0;
   }();
+  // The regular walk inside the direct constant-planes OP_PNP walk (k_assemble_ga<..., REG = 1>):
+  // PNP_ASM_REGULAR=0/1, read once per process.
+  static const bool regular_on = [] {
+    const char *e = getenv("PNP_ASM_REGULAR");
+    return e ? atoi(e) != 0 : kAsmRegularDefault;
+  }();
   int piped = 0;
 #define PNP_ASM_CASE(OPK)                                                          \
   case OPK:                                                                        \
@@ -779,6 +913,10 @@ hipError_t launch_assemble(const DevLayout &L, const AsmArgs &a, hipStream_t s, 
                          block, size_t(L.unmax) * asm_lds_rec<OPK>() * 8, s, t0, t1, 0, L, a); \
     else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst && pipe_on)         \
       piped = launch_pipe<OPK>(L, a, pipe_cap, s, t0, t1);                         \
+    else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst && regular_on)      \
+      hipExtLaunchKernelGGL(                                                       \
+          (k_assemble_ga<OPK, 1, 3, 9, 6, 0, 0, asm_kc<OPK>(), 0, asm_reg<OPK>()>), grid, block, \
+          0, s, t0, t1, 0, L, a);                                                  \
     else if (ga == 4 && fanr == 9 && asm_kc<OPK>() && a.kconst)                    \
       hipExtLaunchKernelGGL((k_assemble_ga<OPK, 1, 3, 9, 6, 0, 0, asm_kc<OPK>()>), grid,  \
                          block, 0, s, t0, t1, 0, L, a);                             \

@@ -3169,6 +3169,15 @@ extern "C" int pnp_asm_info(pnp_ctx *c, int64_t *full, int64_t *reused, int64_t 
   return PNP_OK;
 }
 
+extern "C" int pnp_asm_regular_info(pnp_ctx *c, int64_t *chunks, int64_t *regular_chunks) {
+  if (!c) return PNP_E_ARG;
+  long long n = 0, r = 0;
+  pnp::regular_chunks(c->L, n, r);
+  if (chunks) *chunks = n;
+  if (regular_chunks) *regular_chunks = r;
+  return PNP_OK;
+}
+
 extern "C" int pnp_amg_configure(pnp_ctx *c, const pnp_amg_opts *o) {
   if (!c || !o) return PNP_E_ARG;
   if (o->smoother != PNP_PREC_SSOR && o->smoother != PNP_PREC_ILU0 &&
@@ -3626,6 +3635,15 @@ extern "C" int pnp_state_get(pnp_ctx *c, double *x) {
   return c->download_ext(c->x.p, c->nf, x);
 }
 
+extern "C" int pnp_state_residual(pnp_ctx *c, double *r) {
+  if (!c || !r) return PNP_E_ARG;
+  if (c->kind < 0) return c->fail(PNP_E_STATE, "no operator set");
+  if (c->seq_on() || c->degree > 1)
+    return c->fail(PNP_E_STATE, "pnp_state_residual: P1 contexts, not in reference-order mode");
+  hipSetDevice(c->device);
+  return c->download_ext(c->r.p, c->nf, r);
+}
+
 extern "C" int pnp_assemble_state(pnp_ctx *c, int32_t n) {
   if (!c) return PNP_E_ARG;
   hipSetDevice(c->device);
@@ -3891,6 +3909,16 @@ extern "C" int pnp_layout_view(const pnp_layout_buf *b, pnp_layout *v) {
   v->send_ptr = L.send_ptr.data();
   v->send_idx = L.send_idx.data();
   v->color_conflicts = L.conflicts;
+  return PNP_OK;
+}
+
+extern "C" int pnp_layout_regular_info(const pnp_layout_buf *b, int64_t *chunks,
+                                       int64_t *regular_chunks) {
+  if (!b) return PNP_E_ARG;
+  long long n = 0, r = 0;
+  pnp::regular_chunks(b->L, n, r);
+  if (chunks) *chunks = n;
+  if (regular_chunks) *regular_chunks = r;
   return PNP_OK;
 }
 

@@ -9,6 +9,7 @@
 //   RCB partition, colouring, Morton order and the SELL-64 block layout of the local problem.
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 
 #include <array>
@@ -123,6 +124,23 @@ struct LocalLayout {
   std::vector<int> nbr_ranks;
   std::vector<int> recv_ptr, send_ptr, send_idx;
 };
+
+// The PNP assembly's regular walk (assemble.hip, k_assemble_ga<..., REG = 1>): a row is regular
+// when its fan is closed, has six neighbours (7 slots) and no break; a chunk (one wave) is regular
+// when all its rows are -- the kernel's wave vote, restated on the host.
+static inline bool meta_regular(uint64_t m) {
+  return meta_len(m) == 7 && meta_closed(m) && (m >> 8) == 0;
+}
+static inline void regular_chunks(const LocalLayout &L, long long &chunks, long long &regular) {
+  chunks = L.nchunks;
+  regular = 0;
+  for (int c = 0; c < L.nchunks; c++) {
+    bool all = true;
+    for (int i = c * kChunk; i < std::min((c + 1) * kChunk, L.n_owned) && all; i++)
+      all = meta_regular(L.rowmeta[i]);
+    regular += all;
+  }
+}
 
 // PNP_CREATE_ABSORB_THIN_COLOR (pnp_set_create_option): -1 default (on, unless the environment
 // variable PNP_COLOR_CONFLICTS=0), 0 off, 1 on -- read by build_local_layout

@@ -42,6 +42,7 @@ METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES, METHOD_IDR = 0, 1, 2, 3
 # environment variables of the library, read once per process (include/pnp_capi.h, pnp_asm_info):
 # the persistent, prefetching PNP assembly walk on / off, and a cap on its grid (A/B, tests)
 ASM_PIPE_ENV, ASM_PIPE_GRID_ENV = "PNP_ASM_PIPE", "PNP_ASM_PIPE_GRID"
+ASM_REGULAR_ENV = "PNP_ASM_REGULAR"  # 0/1: the regular walk of the warm OP_PNP assembly (default 1)
 ROW_FLAG_LOAD = 8  # PNP_ROW_FLAG_LOAD
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
@@ -504,6 +505,10 @@ class Layout:
         self.send_ptr = arr(v.send_ptr, v.nnbr + 1)
         self.send_idx = arr(v.send_idx, int(self.send_ptr[-1]) if v.nnbr else 0)
         self.color_conflicts = int(v.color_conflicts)
+        n, r = C.c_int64(0), C.c_int64(0)
+        _check(lib().pnp_layout_regular_info(buf, C.byref(n), C.byref(r)))
+        # pnp_asm_regular_info's counts: 64-row chunks, and those the assembly's regular walk takes
+        self.regular_info = {"chunks": n.value, "regular_chunks": r.value}
         lib().pnp_layout_free(buf)
 
     def row_len(self, i):
@@ -844,6 +849,13 @@ class Context:
         self._ck(lib().pnp_state_get(self.h, _ptr(x)))
         return x
 
+    def state_residual(self):
+        """pnp_state_residual: the residual the last assembly left on the device -- after
+        jacobian() or assemble_state() the one the fused launch wrote with the blocks."""
+        r = np.zeros(self.nf * self.nn)
+        self._ck(lib().pnp_state_residual(self.h, _ptr(r)))
+        return r
+
     def assemble_state(self, n=1):
         self._ck(lib().pnp_assemble_state(self.h, int(n)))
 
@@ -881,6 +893,14 @@ class Context:
         f, r, p = C.c_int64(), C.c_int64(), C.c_int64()
         self._ck(lib().pnp_asm_info(self.h, C.byref(f), C.byref(r), C.byref(p)))
         return {"full": f.value, "reused": r.value, "pipelined": p.value}
+
+    def asm_regular_info(self):
+        """pnp_asm_regular_info: {"chunks": 64-row chunks of this rank's layout, "regular_chunks":
+        those whose rows are all closed six-neighbour fans without a break -- the waves that take
+        the regular walk of the warm OP_PNP assembly (ASM_REGULAR_ENV)}."""
+        n, r = C.c_int64(0), C.c_int64(0)
+        self._ck(lib().pnp_asm_regular_info(self.h, C.byref(n), C.byref(r)))
+        return {"chunks": n.value, "regular_chunks": r.value}
 
     def asm_row_flags(self):
         """pnp_asm_row_flags: the assembly's flag byte per vertex of the operator set now (bits

@@ -522,6 +522,14 @@ int pnp_set_option(pnp_ctx *ctx, int32_t option, int64_t value);
  * process, chooses it for the warm constant-planes assembly; PNP_ASM_PIPE_GRID=n caps its grid at
  * n workgroups).  Any pointer may be NULL. */
 int pnp_asm_info(pnp_ctx *ctx, int64_t *full, int64_t *reused, int64_t *pipelined);
+/* The PNP assembly's regular walk: in the warm constant-planes OP_PNP Jacobian
+ * launch, a 64-row chunk (one wave) whose rows are all closed fans of six neighbours without a
+ * break walks them with static slots; every other chunk takes the general walk.  The environment
+ * variable PNP_ASM_REGULAR=0/1, read once per process, turns it off / on (default on); results are
+ * bitwise the same either way.  chunks: the 64-row chunks of this rank's layout (the last may be
+ * partial); regular_chunks: those the regular walk takes, counted on the host from the layout's
+ * rowmeta with the kernel's predicate.  Either pointer may be NULL. */
+int pnp_asm_regular_info(pnp_ctx *ctx, int64_t *chunks, int64_t *regular_chunks);
 /* The flag byte per vertex that the P1 assembly's residual tail reads for the operator set now,
  * flags[nv_global] in global vertex order (0xff: not a row of this rank).  Bits 0 .. nfields-1: the
  * row's Dirichlet mask; bit 3 (PNP_ROW_FLAG_LOAD): some entry of the row's constant load (Neumann
@@ -682,6 +690,9 @@ int pnp_md_run(pnp_ctx *ctx, double *u, const pnp_md_opts *opts, int32_t nsurf, 
 /* upload x (external layout) into the context's state vector */
 int pnp_state_set(pnp_ctx *ctx, const double *x);
 int pnp_state_get(pnp_ctx *ctx, double *x);
+/* the residual the last assembly left on the device (pnp_assemble_state, pnp_jacobian -- the fused
+ * launch writes it with the blocks --, pnp_residual), as pnp_residual returns it */
+int pnp_state_residual(pnp_ctx *ctx, double *r);
 /* n fused residual+Jacobian assemblies of the state vector, on the device */
 int pnp_assemble_state(pnp_ctx *ctx, int32_t n);  /* n < 0: |n| residual-only assemblies */
 /* the same, with the device time of the whole batch from one HIP event pair around it (ms) */
@@ -754,6 +765,8 @@ typedef struct {
 /* the partition + local layout pnp_create would build for (rank, nranks) */
 int pnp_layout_build(const pnp_mesh *mesh, int32_t rank, int32_t nranks, pnp_layout_buf **out);
 int pnp_layout_view(const pnp_layout_buf *b, pnp_layout *view);
+/* pnp_asm_regular_info's counts for this layout (no context, no GPU) */
+int pnp_layout_regular_info(const pnp_layout_buf *b, int64_t *chunks, int64_t *regular_chunks);
 void pnp_layout_free(pnp_layout_buf *b);
 
 #ifdef __cplusplus

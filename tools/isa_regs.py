@@ -1,19 +1,22 @@
 """Per-kernel VGPR / spill / scratch counts of a HIP source for gfx950 (device-only asm, no GPU
 needed), and with --fp64 each kernel's fp64 VALU instruction multiset (two instantiations compute
 the same arithmetic only if the compiler contracted them alike: compare their multisets).
-usage: python tools/isa_regs.py dune-pnp_amd/csrc/assemble.hip [name-filter] [--fp64]"""
+A -DNAME argument goes to the compiler (assemble.hip's -DASM_REGULAR_CHECK: the regular walk
+alone in its kernels, next to the general walk unrolled for six neighbours).
+usage: python tools/isa_regs.py dune-pnp_amd/csrc/assemble.hip [name-filter] [--fp64] [-DNAME]"""
 import collections
 import re
 import subprocess
 import sys
 
-args = [a for a in sys.argv[1:] if a != "--fp64"]
+defs = [a for a in sys.argv[1:] if a.startswith("-D")]
+args = [a for a in sys.argv[1:] if a != "--fp64" and a not in defs]
 fp64 = "--fp64" in sys.argv[1:]
 src = args[0]
 filt = args[1] if len(args) > 1 else ""
 out = "/tmp/isa_regs.s"
 subprocess.check_call(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                       "-munsafe-fp-atomics", "--cuda-device-only", "-S", "-o", out, src],
+                       "-munsafe-fp-atomics", "--cuda-device-only", "-S", "-o", out, src] + defs,
                       stderr=subprocess.DEVNULL)
 txt = open(out).read()
 
