@@ -1515,7 +1515,7 @@ int pnp_ctx::amg_apply(const double *d, double *vout) {
   const bool pre0 = amg_opts.level0_presmooth > 0 ||
                     (amg_opts.level0_presmooth < 0 && amg_symmetric);
   if (pre0) {
-    if ((rc = smoother(sm, d, amg_x0.p))) return rc;
+    if ((rc = smoother(sm, d, amg_x0.p, true))) return rc;
     e = pnp::launch_spmv(dl, nf, pat, vals.p, amg_x0.p, amg_t.p, 3, d, partials.p, &nsp,
                          stream);
   } else {
@@ -1571,7 +1571,7 @@ int pnp_ctx::amg_apply(const double *d, double *vout) {
                                amg_z.p, stream, 0, amg_y.p, vout, f32_now(), ilu_y32());
     return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
   }
-  if ((rc = smoother(sm, amg_r.p, amg_z.p))) return rc;
+  if ((rc = smoother(sm, amg_r.p, amg_z.p, true))) return rc;
   e = pnp::launch_axpby(nn, 1.0, amg_y.p, 1.0, amg_z.p, vout, stream);
   return e == hipSuccess ? PNP_OK : hipfail(e, "amg v-cycle");
 }
@@ -2978,7 +2978,7 @@ extern "C" int pnp_linear_solve(pnp_ctx *c, const double *rhs, double *z, const 
 }
 
 extern "C" int pnp_prec_apply(pnp_ctx *c, int32_t prec, const double *d, double *v) {
-  if (!c || !d || !v || prec < PNP_PREC_NONE || prec > PNP_PREC_SSOR_NATURAL) return PNP_E_ARG;
+  if (!c || !d || !v || prec < PNP_PREC_NONE || prec > PNP_PREC_CHEBYSHEV) return PNP_E_ARG;
   if (!c->assembled) return c->fail(PNP_E_STATE, "no Jacobian assembled");
   hipSetDevice(c->device);
   int rc;
@@ -3181,8 +3181,10 @@ extern "C" int pnp_asm_regular_info(pnp_ctx *c, int64_t *chunks, int64_t *regula
 extern "C" int pnp_amg_configure(pnp_ctx *c, const pnp_amg_opts *o) {
   if (!c || !o) return PNP_E_ARG;
   if (o->smoother != PNP_PREC_SSOR && o->smoother != PNP_PREC_ILU0 &&
-      o->smoother != PNP_PREC_JACOBI && o->smoother != PNP_PREC_SSOR_NATURAL)
-    return c->fail(PNP_E_ARG, "AMG smoother must be SSOR, SSOR_NATURAL, ILU0 or JACOBI");
+      o->smoother != PNP_PREC_JACOBI && o->smoother != PNP_PREC_SSOR_NATURAL &&
+      o->smoother != PNP_PREC_CHEBYSHEV)
+    return c->fail(PNP_E_ARG,
+                   "AMG smoother must be SSOR, SSOR_NATURAL, ILU0, JACOBI or CHEBYSHEV");
   if (o->coarse_target < 1 || o->coarse_target > pnp::kAmgMaxCoarse || o->max_levels < 2 ||
       o->max_levels > pnp::kAmgMaxLevels || !(o->omega > 0 && o->omega <= 2) ||
       o->coarse_sweeps < 1 || o->coarse_sweeps > 8 || o->level0_presmooth < -1 ||
@@ -3193,6 +3195,36 @@ extern "C" int pnp_amg_configure(pnp_ctx *c, const pnp_amg_opts *o) {
   c->amg_opts = *o;
   if (rebuild) c->amg_built = false;
   c->amg_values_drop();
+  return PNP_OK;
+}
+
+extern "C" int pnp_cheb_configure(pnp_ctx *c, const pnp_cheb_opts *o) {
+  if (!c) return PNP_E_ARG;
+  const pnp_cheb_opts def{3, 10.0, 20, 1.1, 0.0};
+  if (!o) o = &def;
+  if (!pnp::cheb_opts_valid(o->steps, o->eig_ratio, o->eig_iters, o->eig_boost, o->lambda_max))
+    return c->fail(PNP_E_ARG, "Chebyshev options out of range: steps 1 .. 16, eig_ratio > 1, "
+                              "eig_iters 1 .. 100, eig_boost >= 1, lambda_max >= 0");
+  c->cheb_opts = *o;
+  // the estimate and the coefficients go; steps enters the launches by value, so the graphs go too
+  c->cheb_valid = false;
+  c->cheb_lest = c->cheb_lmax = c->cheb_lmin = 0;
+  hipSetDevice(c->device);
+  c->graphs_clear();
+  return PNP_OK;
+}
+
+extern "C" int pnp_cheb_info(pnp_ctx *c, pnp_cheb_stats *st) {
+  if (!c || !st) return PNP_E_ARG;
+  std::memset(st, 0, sizeof *st);
+  st->steps = c->cheb_opts.steps;
+  st->lambda_est = c->cheb_lest;
+  st->lambda_max = c->cheb_lmax;
+  st->lambda_min = c->cheb_lmin;
+  st->applies = c->cheb_applies;
+  st->estimates = c->cheb_estimates;
+  st->fused_steps = c->cheb_fused;
+  st->unfused_steps = c->cheb_unfused;
   return PNP_OK;
 }
 

@@ -25,6 +25,7 @@
 
 #include "../../include/pnp_capi.h"
 #include "amg.h"
+#include "cheb_small.h"
 #include "gmres_small.h"
 #include "idr_small.h"
 #include "kernels.h"
@@ -158,6 +159,9 @@ struct pnp_ctx {
   //                   split and ilu_factor set; derived_drop clears, ilu_factors_drop clears a 2
   //   amg_valid       the AMG's coarse values come from it: amg_setup sets; derived_drop and
   //                   amg_values_drop (pnp_amg_configure) clear
+  //   cheb_valid      cheb_coef holds the Chebyshev coefficients for its bounds (estimated from it,
+  //                   or the caller's) and the configured steps: cheb_prepare sets; derived_drop and
+  //                   pnp_cheb_configure clear
   // and of the operator itself:
   //   vals_const_valid  vals holds the PNP k-form's state-independent planes for the operator set
   //                   now: set by a P1 analytic assembly that wrote every plane (asm_wrote), cleared
@@ -167,7 +171,7 @@ struct pnp_ctx {
   //   seq_op_valid    the reference-order copies of the operator are on the device: seq_prepare sets,
   //                   op_activate clears
   bool assembled = false, mf_lin = false, vals_stale = false, mf_diag_valid = false;
-  bool csr_vals_valid = false, lu_valid = false, amg_valid = false;
+  bool csr_vals_valid = false, lu_valid = false, amg_valid = false, cheb_valid = false;
   int split_of = 0;
   bool vals_const_valid = false, seq_op_valid = false;
   // what is computed from the stored Jacobian's values
@@ -175,6 +179,7 @@ struct pnp_ctx {
     lu_valid = false;
     split_of = 0;
     amg_valid = false;
+    cheb_valid = false;
   }
   void amg_values_drop() { amg_valid = false; }
   // the factors are recomputed (another factorisation path or precision); a split matrix stays
@@ -457,6 +462,22 @@ struct pnp_ctx {
   DBuf<int> amg_ipiv, amg_info;
   rocblas_handle blas = nullptr;  // rocSOLVER getrf/getri of the AMG's coarsest level
 
+  // ---- Chebyshev polynomial preconditioner (PNP_PREC_CHEBYSHEV) ----------------
+  // cheb_p: the double-buffered direction with its ghosts (zeroed once; the stand-alone form
+  // exchanges them per step, the AMG's rank-local form keeps them zero); cheb_r: the recurrence's
+  // residual; cheb_t: A p of the unfused step; cheb_coef: the coefficients the kernels read
+  // (cheb_small.h), rewritten by cheb_prepare, so that a captured graph outlives a new Jacobian
+  pnp_cheb_opts cheb_opts{3, 10.0, 20, 1.1, 0.0};
+  DBuf<double> cheb_r, cheb_t, cheb_p[2], cheb_coef;
+  double cheb_hcoef[pnp::kChebCoefDoubles] = {0};
+  double cheb_lest = 0, cheb_lmax = 0, cheb_lmin = 0;  // the bounds last used (pnp_cheb_info)
+  bool cheb_ghosts_dirty = false;  // a stand-alone application has written the ghosts of cheb_p
+  long long cheb_applies = 0, cheb_estimates = 0, cheb_fused = 0, cheb_unfused = 0;
+  int cheb_estimate(double &lest);
+  int cheb_prepare();
+  // local: the owned x owned operator without a halo (inside amg_apply), else the global one
+  int cheb_apply(const double *d, double *vout, bool local);
+
   // vectors (sized n_local * 3)
   DBuf<double> x, r, rs, z, rt, p, v, t, y, y2, b, prevu, ext, sendbuf, partials, partials2;
   DBuf<double> redmw;  // the multi-workgroup reduction's ticket and slice sums (main stream only)
@@ -700,7 +721,7 @@ struct pnp_ctx {
   void solve_result(pnp_solve_result &res, int done, int breakdown, int it, double it_half,
                     double norm0, double norm, double t_start);
   int history_download(const double *dev, int count);
-  int smoother(int prec, const double *d, double *vout);
+  int smoother(int prec, const double *d, double *vout, bool in_amg = false);
   int precond(int prec, const double *d, double *vout);
   int bicgstab(const double *bdev, double *zout, const pnp_solve_opts &o, pnp_solve_result &res,
                int fixed);

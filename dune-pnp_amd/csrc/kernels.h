@@ -360,6 +360,29 @@ hipError_t launch_jac_diag(const DevLayout &L, const AsmArgs &a, double *dvals, 
 // preconditioners: v = M^{-1} d (v over owned rows)
 hipError_t launch_jacobi(const DevLayout &L, int nf, int pat, const double *vals, const double *d,
                          double *v, hipStream_t s);
+// Chebyshev polynomial preconditioner on vertex-block Jacobi (PNP_PREC_CHEBYSHEV; the recurrence and
+// the layout of the device coefficients coef in cheb_small.h).  vals / L.chunk_off: the SELL values,
+// or the diagonal blocks of launch_jac_diag through a layout whose chunk_off[c] = 64 c.
+// first: z = p0 = D^-1 d / theta; coef null: z = D^-1 d (steps 1, the power iteration); p0 null: z only
+hipError_t launch_cheb_first(const DevLayout &L, int nf, int pat, const double *vals,
+                             const double *d, const double *coef, double *p0, double *z,
+                             hipStream_t s);
+// step >= 1 from t = A p_old: r_out = r_in - t (not stored when last), p_new = a p_old + b D^-1 r,
+// z += p_new (owned rows; p_new is not p_old)
+hipError_t launch_cheb_update(const DevLayout &L, int nf, int pat, const double *vals,
+                              const double *coef, int step, int last, const double *r_in,
+                              const double *t, double *r_out, const double *p_old, double *p_new,
+                              double *z, hipStream_t s);
+// the same step as one launch, the LDS-staged SpMV on p_old (with its ghosts) and the tail;
+// whole-matrix launches on layouts with cheb_can_fuse() only (hipErrorInvalidValue otherwise)
+hipError_t launch_cheb_step(const DevLayout &L, int nf, int pat, const double *vals,
+                            const double *coef, int step, int last, const double *r_in,
+                            double *r_out, const double *p_old, double *p_new, double *z,
+                            hipStream_t s);
+// the layout carries the SpMV's LDS lists and the environment variable PNP_CHEB_FUSED is not 0
+bool cheb_can_fuse(const DevLayout &L);
+// w[i * nf + f] = idr_shadow_entry(l2g[i], 4, f), owned rows: the power iteration's start
+hipError_t launch_cheb_w0(int n_owned, int nf, const int *l2g, double *w, hipStream_t s);
 // symmetric multicolour Gauss-Seidel on the split matrix (lv, uv); t = scratch [n_owned * nf]
 hipError_t launch_sgs(const DevLayout &L, const int *color_ptr_host, int nf, int pat,  // NOLINT
                       const double *lv, const double *uv, const double *d, double *v, double *t,

@@ -11,7 +11,133 @@ int pnp_ctx::prec_prepare(int prec) {
   if (prec == PNP_PREC_SSOR) rc = split(1);
   if (prec == PNP_PREC_SSOR_NATURAL) rc = csr_values();
   if (prec == PNP_PREC_AMG) rc = amg_setup();
+  // Chebyshev: the diagonal blocks (of their own walk while the SELL values are stale), then the
+  // bounds and coefficients
+  if (prec == PNP_PREC_CHEBYSHEV && !(rc = jacobi_prepare())) rc = cheb_prepare();
   return rc;
+}
+
+// ---- Chebyshev polynomial preconditioner (kernels in linalg.hip) ---------------
+// where the diagonal blocks are read from: the SELL values, or, for a Jacobian held as a
+// linearisation point whose values nobody needed yet, the blocks of jacobi_prepare()
+static const double *cheb_diag(pnp_ctx *c, pnp::DevLayout &Ld) {
+  Ld = c->dl;
+  if (c->mf_lin && c->vals_stale) {
+    Ld.chunk_off = c->mf_choff.p;
+    return c->mf_diag.p;
+  }
+  return c->vals.p;
+}
+
+// lambda_est = |w_m| / |w_{m-1}|, w_j = D^-1 A w_{j-1} with halo, no normalisation in between
+// (m <= 100 stays inside the fp64 range); the two norms are read at the end
+int pnp_ctx::cheb_estimate(double &lest) {
+  pnp::DevLayout Ld;
+  const double *dv = cheb_diag(this, Ld);
+  if (mf_lin && vals_stale && !mf_diag_valid)
+    return fail(PNP_E_STATE, "Chebyshev: no diagonal (jacobi_prepare)");
+  const int m = cheb_opts.eig_iters;
+  int nsp = 0, rc;
+  hipError_t e = pnp::launch_cheb_w0(L.n_owned, nf, d_l2g.p, cheb_p[0].p, stream);
+  for (int j = 1; j <= m && e == hipSuccess; j++) {
+    double *w = cheb_p[(j - 1) & 1].p, *wn = cheb_p[j & 1].p;
+    if ((rc = halo_spmv(w, cheb_t.p, 0, nullptr, nullptr, &nsp))) return rc;
+    e = pnp::launch_cheb_first(Ld, nf, pat, dv, cheb_t.p, nullptr, nullptr, wn, stream);
+  }
+  if (e != hipSuccess) return hipfail(e, "chebyshev estimate");
+  cheb_ghosts_dirty = true;
+  double n0 = 0, n1 = 0;
+  if ((rc = norm(cheb_p[(m - 1) & 1].p, n0)) || (rc = norm(cheb_p[m & 1].p, n1))) return rc;
+  lest = n0 > 0 ? n1 / n0 : 0.0;
+  cheb_estimates++;
+  return PNP_OK;
+}
+
+// buffers (once), then per stored Jacobian and configuration: bounds, coefficients on the device
+int pnp_ctx::cheb_prepare() {
+  if (!assembled) return fail(PNP_E_STATE, "no Jacobian assembled");
+  if (cheb_valid) return PNP_OK;
+  if (!cheb_coef.p) {
+    const size_t nl = std::max<size_t>(1, size_t(dl.n_local) * 3);
+    hipError_t e;
+    if ((e = cheb_r.alloc(nl)) != hipSuccess || (e = cheb_t.alloc(nl)) != hipSuccess ||
+        (e = cheb_p[0].alloc(nl)) != hipSuccess || (e = cheb_p[1].alloc(nl)) != hipSuccess ||
+        (e = cheb_coef.alloc(pnp::kChebCoefDoubles)) != hipSuccess)
+      return hipfail(e, "chebyshev buffers");
+  }
+  cheb_lest = cheb_lmax = cheb_lmin = 0;
+  if (cheb_opts.steps >= 2) {
+    double lest = 0;
+    if (!(cheb_opts.lambda_max > 0)) {
+      hipEvent_t t0 = tb(T_FACT);
+      if (int rc = cheb_estimate(lest)) return rc;
+      te(T_FACT, t0);
+    }
+    double lmax, lmin;
+    if (!pnp::cheb_bounds(cheb_opts.lambda_max, lest, cheb_opts.eig_boost, cheb_opts.eig_ratio,
+                          lmax, lmin) ||
+        !pnp::cheb_coefficients(cheb_opts.steps, lmax, lmin, cheb_hcoef))
+      return fail(PNP_E_STATE, "Chebyshev: the eigenvalue estimate is zero or not finite");
+    // (synchronous: the staging array may be rewritten by the next prepare)
+    hipError_t e = hipMemcpyAsync(cheb_coef.p, cheb_hcoef, sizeof cheb_hcoef,
+                                  hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e != hipSuccess) return hipfail(e, "chebyshev coefficients");
+    cheb_lest = lest;
+    cheb_lmax = lmax;
+    cheb_lmin = lmin;
+  }
+  cheb_valid = true;
+  return PNP_OK;
+}
+
+int pnp_ctx::cheb_apply(const double *d, double *vout, bool local) {
+  if (!cheb_valid) return fail(PNP_E_STATE, "Chebyshev: not prepared (cheb_prepare)");
+  const int k = cheb_opts.steps;
+  pnp::DevLayout Ld;
+  const double *dv = cheb_diag(this, Ld);
+  if (mf_lin && vals_stale && !mf_diag_valid)
+    return fail(PNP_E_STATE, "Chebyshev: no diagonal (jacobi_prepare)");
+  hipError_t e = hipSuccess;
+  cheb_applies++;
+  if (local && cheb_ghosts_dirty && L.n_ghost > 0 && k > 1) {  // the rank-local form's zero ghosts
+    const size_t off = size_t(L.n_owned) * nf, bytes = sizeof(double) * size_t(L.n_ghost) * nf;
+    e = hipMemsetAsync(cheb_p[0].p + off, 0, bytes, stream);
+    if (e == hipSuccess) e = hipMemsetAsync(cheb_p[1].p + off, 0, bytes, stream);
+    if (e != hipSuccess) return hipfail(e, "chebyshev ghosts");
+    cheb_ghosts_dirty = false;
+  }
+  e = pnp::launch_cheb_first(Ld, nf, pat, dv, d, k > 1 ? cheb_coef.p : nullptr,
+                             k > 1 ? cheb_p[0].p : nullptr, vout, stream);
+  if (e != hipSuccess) return hipfail(e, "chebyshev first step");
+  // the fused step reads the SELL values on this rank's rows and columns: one rank (or the
+  // rank-local form), assembled values, a layout with the SpMV's LDS lists
+  const bool fused = pnp::cheb_can_fuse(dl) && !(mf_lin && vals_stale) && (local || nranks == 1);
+  for (int i = 1; i < k; i++) {
+    double *po = cheb_p[(i - 1) & 1].p, *pn = cheb_p[i & 1].p;
+    const double *rin = i == 1 ? d : cheb_r.p;  // step 1 reads d: it is never copied
+    const int last = i == k - 1 ? 1 : 0;
+    if (fused) {
+      e = pnp::launch_cheb_step(dl, nf, pat, vals.p, cheb_coef.p, i, last, rin, cheb_r.p, po, pn,
+                                vout, stream);
+      cheb_fused++;
+    } else {
+      int nsp = 0;
+      if (local) {
+        e = pnp::launch_spmv(dl, nf, pat, vals.p, po, cheb_t.p, 0, nullptr, partials.p, &nsp,
+                             stream);
+        if (e != hipSuccess) return hipfail(e, "chebyshev spmv");
+      } else {
+        if (int rc = halo_spmv(po, cheb_t.p, 0, nullptr, nullptr, &nsp)) return rc;
+        if (nranks > 1) cheb_ghosts_dirty = true;
+      }
+      e = pnp::launch_cheb_update(Ld, nf, pat, dv, cheb_coef.p, i, last, rin, cheb_t.p, cheb_r.p,
+                                  po, pn, vout, stream);
+      cheb_unfused++;
+    }
+    if (e != hipSuccess) return hipfail(e, "chebyshev step");
+  }
+  return PNP_OK;
 }
 
 // every solver's start: zout = 0, rs = b
@@ -71,9 +197,11 @@ int pnp_ctx::history_download(const double *dev, int count) {
 }
 
 // the single-level preconditioners, untimed, prerequisites (split / factors) in place
-int pnp_ctx::smoother(int prec, const double *d, double *vout) {
+int pnp_ctx::smoother(int prec, const double *d, double *vout, bool in_amg) {
   hipError_t e = hipSuccess;
-  if (prec == PNP_PREC_JACOBI && mf_lin && vals_stale) {
+  if (prec == PNP_PREC_CHEBYSHEV) {
+    return cheb_apply(d, vout, in_amg);
+  } else if (prec == PNP_PREC_JACOBI && mf_lin && vals_stale) {
     // no SELL values: the diagonal blocks of jacobi_prepare(), one slot per chunk
     if (!mf_diag_valid) return fail(PNP_E_STATE, "Jacobi: no diagonal (jacobi_prepare)");
     pnp::DevLayout dv = dl;

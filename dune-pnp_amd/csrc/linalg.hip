@@ -20,6 +20,7 @@
 
 #include <hip/hip_ext.h>
 
+#include "idr_small.h"
 #include "kernels.h"
 
 // split sweeps: issue a batch's L/U value loads with its column-index loads (1) or after them (0)
@@ -369,6 +370,259 @@ __global__ __launch_bounds__(kBlock) void k_jacobi(DevLayout L, const double *__
   mask_rows<NF, PAT>(D, row_mask<NF>(L, row), true);
 #pragma unroll
   for (int f = 0; f < NF; f++) v[size_t(row) * NF + f] = d[size_t(row) * NF + f] / D[pat_index(PAT, f, f)];
+}
+
+// ------------------------------------------------------------------------------------------
+// Chebyshev polynomial preconditioner on vertex-block Jacobi (PNP_PREC_CHEBYSHEV; DESIGN.md 4.13,
+// cheb_small.h for the recurrence and the layout of coef)
+// ------------------------------------------------------------------------------------------
+// r <- D^-1 r with D the row's diagonal block (slot 0's k-form record Kd, expanded, Dirichlet rows
+// identity rows): Gaussian elimination with partial pivoting, static indices only (registers)
+template <int NF, int PAT>
+__device__ __forceinline__ void cheb_block_solve(const double *Kd, unsigned dm, double (&r)[NF]) {
+  constexpr int NV = popc9(PAT);
+  double D[NV];
+  expand_k<PAT>(Kd, D);
+  mask_rows<NF, PAT>(D, dm, true);
+  if constexpr (NF == 1) {
+    r[0] = r[0] / D[0];
+  } else {
+    double A[NF][NF];
+#pragma unroll
+    for (int f = 0; f < NF; f++)
+#pragma unroll
+      for (int g = 0; g < NF; g++) {
+        const int v = pat_index(PAT, f, g);
+        A[f][g] = v >= 0 ? D[v < 0 ? 0 : v] : 0.0;
+      }
+#pragma unroll
+    for (int k = 0; k < NF; k++) {
+#pragma unroll
+      for (int i = k + 1; i < NF; i++) {  // the largest pivot candidate bubbles into row k
+        const bool sw = fabs(A[i][k]) > fabs(A[k][k]);
+#pragma unroll
+        for (int j = 0; j < NF; j++) {
+          const double t = A[k][j];
+          A[k][j] = sw ? A[i][j] : t;
+          A[i][j] = sw ? t : A[i][j];
+        }
+        const double t = r[k];
+        r[k] = sw ? r[i] : t;
+        r[i] = sw ? t : r[i];
+      }
+      const double inv = 1.0 / A[k][k];
+#pragma unroll
+      for (int i = k + 1; i < NF; i++) {
+        const double m = A[i][k] * inv;
+#pragma unroll
+        for (int j = k + 1; j < NF; j++) A[i][j] -= m * A[k][j];
+        r[i] -= m * r[k];
+      }
+    }
+#pragma unroll
+    for (int k = NF - 1; k >= 0; k--) {
+      double s = r[k];
+#pragma unroll
+      for (int j = k + 1; j < NF; j++) s -= A[k][j] * r[j];
+      r[k] = s / A[k][k];
+    }
+  }
+}
+
+// the first step: z = p0 = D^-1 d / theta (coef[0] = 1 / theta); coef null: z = D^-1 d alone
+// (steps 1, and the power iteration's D^-1); p0 null: not written
+template <int NF, int PAT>
+__global__ __launch_bounds__(kBlock) void k_cheb_first(DevLayout L, const double *__restrict__ vals,
+                                                       const double *__restrict__ d,
+                                                       const double *__restrict__ coef,
+                                                       double *__restrict__ p0,
+                                                       double *__restrict__ z) {
+  constexpr int NK = nks_of(PAT);
+  const int row = blockIdx.x * kBlock + threadIdx.x;
+  if (row >= L.n_owned) return;
+  const int chunk = row / kRows, lane = row % kRows;
+  double K[NK], g[NF];
+  load_vals<NK>(vals + size_t(L.chunk_off[chunk]) * NK, lane, K);
+  load_nf<NF>(d, size_t(row), g);
+  cheb_block_solve<NF, PAT>(K, row_mask<NF>(L, row), g);
+  if (coef) {
+    const double it = coef[0];
+#pragma unroll
+    for (int f = 0; f < NF; f++) g[f] *= it;
+  }
+  if (p0) store_nf<NF>(p0, size_t(row), g);
+  store_nf<NF>(z, size_t(row), g);
+}
+
+// step i >= 1 of a live row from acc = (A p_old)_row: r = r_in - acc (stored unless it is the last
+// step), p_new = a_i p_old + b_i D^-1 r, z += p_new.  r and z are row-private; p_new is another
+// buffer than p_old, which the neighbours' rows still read
+template <int NF, int PAT>
+__device__ __forceinline__ void cheb_tail(const DevLayout &L, int row, const double *Kd,
+                                          const double (&acc)[NF], const double (&po)[NF],
+                                          const double *__restrict__ coef, int step, int last,
+                                          const double *__restrict__ r_in,
+                                          double *__restrict__ r_out, double *__restrict__ p_new,
+                                          double *__restrict__ z) {
+  double r[NF], zr[NF], pn[NF];
+  load_nf<NF>(r_in, size_t(row), r);
+  load_nf<NF>(z, size_t(row), zr);
+#pragma unroll
+  for (int f = 0; f < NF; f++) r[f] -= acc[f];
+  if (!last) store_nf<NF>(r_out, size_t(row), r);
+  cheb_block_solve<NF, PAT>(Kd, row_mask<NF>(L, row), r);
+  const double a = coef[2 * step - 1], b = coef[2 * step];
+#pragma unroll
+  for (int f = 0; f < NF; f++) {
+    pn[f] = a * po[f] + b * r[f];
+    zr[f] += pn[f];
+  }
+  store_nf<NF>(p_new, size_t(row), pn);
+  store_nf<NF>(z, size_t(row), zr);
+}
+
+// the unfused tail: t = A p_old was computed by the operator application before this launch
+template <int NF, int PAT>
+__global__ __launch_bounds__(kBlock) void k_cheb_update(DevLayout L, const double *__restrict__ vals,
+                                                        const double *__restrict__ coef, int step,
+                                                        int last, const double *__restrict__ r_in,
+                                                        const double *__restrict__ t,
+                                                        double *__restrict__ r_out,
+                                                        const double *__restrict__ p_old,
+                                                        double *__restrict__ p_new,
+                                                        double *__restrict__ z) {
+  constexpr int NK = nks_of(PAT);
+  const int row = blockIdx.x * kBlock + threadIdx.x;
+  if (row >= L.n_owned) return;
+  const int chunk = row / kRows, lane = row % kRows;
+  double K[NK], acc[NF], po[NF];
+  load_vals<NK>(vals + size_t(L.chunk_off[chunk]) * NK, lane, K);
+  load_nf<NF>(t, size_t(row), acc);
+  load_nf<NF>(p_old, size_t(row), po);
+  cheb_tail<NF, PAT>(L, row, K, acc, po, coef, step, last, r_in, r_out, p_new, z);
+}
+
+// the fused step: k_spmv_lds's staging, slot pairs and Dirichlet rows on x = p_old (mode 0, its
+// arithmetic order), then the tail on the row's accumulator; slot 0's record, which the slot loop
+// loads anyway, is the diagonal block, and the row's own p_old is the SPMV_OWN_DIRECT register (a
+// direct load on layouts without uown).  No hand-off inside the kernel: p_old is only read, p_new
+// only written, r and z are touched by their own row alone
+template <int NF, int PAT, int NT>
+__global__ __launch_bounds__(kBlock) void k_cheb_step_lds(
+    DevLayout L, const double *__restrict__ vals, const double *__restrict__ coef, int step,
+    int last, const double *__restrict__ r_in, double *__restrict__ r_out,
+    const double *__restrict__ x, double *__restrict__ p_new, double *__restrict__ z) {
+  constexpr int NV = popc9(PAT), NK = nks_of(PAT), SB = 2;
+  extern __shared__ double sx[];  // [cnt][NF]
+  const int blk = row_block(L, blockIdx.x, gridDim.x);
+  const int row = blk * kBlock + threadIdx.x;
+  const bool live = row < L.n_owned;
+  const int chunk = row / kRows, lane = row % kRows;
+  const int off = live ? L.chunk_off[chunk] : 0, len = live ? L.chunk_len[chunk] : 0;
+  const int u0 = L.uptr[blk];
+  const int cnt = (SPMV_OWN_DIRECT && L.uown) ? L.uown[blk] : L.uptr[blk + 1] - u0;
+  const uint16_t *__restrict__ lix = L.lidx + off + lane;
+  const double *__restrict__ vc = vals + size_t(off) * NK;
+  double xo[NF];
+#pragma unroll
+  for (int f = 0; f < NF; f++) xo[f] = 0;
+  int lown = -1;
+  if (live) {
+    load_nf<NF>(x, size_t(row), xo);
+    if (SPMV_OWN_DIRECT && L.uown) lown = lix[0];
+  }
+  {  // up to SPMV_SU list entries per thread: list loads, then gathers, then LDS stores
+    int jj[SPMV_SU];
+#pragma unroll
+    for (int u = 0; u < SPMV_SU; u++) {
+      const int k = int(threadIdx.x) + u * kBlock;
+      jj[u] = k < cnt ? L.ulist[u0 + k] : -1;
+    }
+    double t[SPMV_SU][NF];
+#pragma unroll
+    for (int u = 0; u < SPMV_SU; u++)
+      if (jj[u] >= 0) load_nf<NF>(x, size_t(jj[u]), t[u]);
+#pragma unroll
+    for (int u = 0; u < SPMV_SU; u++) {
+      const int k = int(threadIdx.x) + u * kBlock;
+      if (jj[u] >= 0)
+#pragma unroll
+        for (int f = 0; f < NF; f++) sx[k * NF + f] = t[u][f];
+    }
+  }
+  for (int k = int(threadIdx.x) + SPMV_SU * kBlock; k < cnt; k += kBlock) {  // longer lists
+    double t[NF];
+    load_nf<NF>(x, size_t(L.ulist[u0 + k]), t);
+#pragma unroll
+    for (int f = 0; f < NF; f++) sx[k * NF + f] = t[f];
+  }
+  __syncthreads();
+  double Kd[NK];
+#pragma unroll
+  for (int qq = 0; qq < NK; qq++) Kd[qq] = 0.0;
+  double acc2[2][NF];
+#pragma unroll
+  for (int f = 0; f < NF; f++) acc2[0][f] = acc2[1][f] = 0;
+  for (int s0 = 0; s0 < len; s0 += SB) {
+    int li[SB];
+    double k[SB][NK];
+#pragma unroll
+    for (int b = 0; b < SB; b++) {
+      const int sl = s0 + b;
+      li[b] = sl < len ? lix[sl * kRows] : 0;
+      if (sl < len) {
+        if (NT)
+          load_vals_nt<NK>(vc + size_t(sl) * NK * kRows, lane, k[b]);
+        else
+          load_vals<NK>(vc + size_t(sl) * NK * kRows, lane, k[b]);
+      } else {
+#pragma unroll
+        for (int qq = 0; qq < NK; qq++) k[b][qq] = 0.0;
+      }
+    }
+    if (s0 == 0) {
+#pragma unroll
+      for (int qq = 0; qq < NK; qq++) Kd[qq] = k[0][qq];
+    }
+#pragma unroll
+    for (int b = 0; b < SB; b++) {
+      double a[NV], xj[NF];
+      const bool me = SPMV_OWN_DIRECT && li[b] == lown;
+      const int lj = me ? 0 : li[b];
+#pragma unroll
+      for (int g = 0; g < NF; g++) {
+        const double t = sx[lj * NF + g];
+        xj[g] = me ? xo[g] : t;
+      }
+      expand_k<PAT>(k[b], a);
+#pragma unroll
+      for (int f = 0; f < NF; f++)
+#pragma unroll
+        for (int g = 0; g < NF; g++) {
+          const int v = pat_index(PAT, f, g);
+          if (v >= 0) acc2[b][f] += a[v] * xj[g];
+        }
+    }
+  }
+  if (!live) return;
+  double acc[NF];
+#pragma unroll
+  for (int f = 0; f < NF; f++) acc[f] = acc2[0][f] + acc2[1][f];
+  const unsigned dm = row_mask<NF>(L, row);  // Dirichlet rows are identity rows
+#pragma unroll
+  for (int f = 0; f < NF; f++)
+    if ((dm >> f) & 1) acc[f] = xo[f];
+  cheb_tail<NF, PAT>(L, row, Kd, acc, xo, coef, step, last, r_in, r_out, p_new, z);
+}
+
+// the power iteration's start vector: the counter-based entry of idr_small.h at column slot 4,
+// by global node and field (so independent of layout and partition)
+__global__ __launch_bounds__(kBlock) void k_cheb_w0(int n, int nf, const int *__restrict__ l2g,
+                                                    double *__restrict__ w) {
+  const int i = blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const unsigned long long g = (unsigned long long)l2g[i];
+  for (int f = 0; f < nf; f++) w[size_t(i) * nf + f] = idr_shadow_entry(g, 4u, unsigned(f));
 }
 
 // one colour of a Gauss-Seidel sweep: v_i += D_i^{-1} (d_i - sum_j A_ij v_j), rows of the
@@ -2183,6 +2437,61 @@ hipError_t launch_jacobi(const DevLayout &L, int nf, int pat, const double *vals
     hipLaunchKernelGGL((k_jacobi<NFc, PATc>), rows_grid(L.n_owned), dim3(kBlock), 0, s, L, vals,
                        d, v);
   });
+  return hipGetLastError();
+}
+
+// PNP_CHEB_FUSED=0 (read once per process): every Chebyshev step as an operator application and
+// k_cheb_update (A/B and test knob); default: the fused step wherever cheb_can_fuse() holds
+static bool cheb_fused_env() {
+  static const bool v = [] {
+    const char *e = std::getenv("PNP_CHEB_FUSED");
+    return !(e && std::atoi(e) == 0);
+  }();
+  return v;
+}
+bool cheb_can_fuse(const DevLayout &L) { return cheb_fused_env() && spmv_uses_lds(L); }
+
+hipError_t launch_cheb_first(const DevLayout &L, int nf, int pat, const double *vals,
+                             const double *d, const double *coef, double *p0, double *z,
+                             hipStream_t s) {
+  if (L.n_owned == 0) return hipSuccess;
+  PNP_PAT_DISPATCH(nf, pat, {
+    hipLaunchKernelGGL((k_cheb_first<NFc, PATc>), rows_grid(L.n_owned), dim3(kBlock), 0, s, L,
+                       vals, d, coef, p0, z);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_cheb_update(const DevLayout &L, int nf, int pat, const double *vals,
+                              const double *coef, int step, int last, const double *r_in,
+                              const double *t, double *r_out, const double *p_old, double *p_new,
+                              double *z, hipStream_t s) {
+  if (L.n_owned == 0) return hipSuccess;
+  PNP_PAT_DISPATCH(nf, pat, {
+    hipLaunchKernelGGL((k_cheb_update<NFc, PATc>), rows_grid(L.n_owned), dim3(kBlock), 0, s, L,
+                       vals, coef, step, last, r_in, t, r_out, p_old, p_new, z);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_cheb_step(const DevLayout &L, int nf, int pat, const double *vals,
+                            const double *coef, int step, int last, const double *r_in,
+                            double *r_out, const double *p_old, double *p_new, double *z,
+                            hipStream_t s) {
+  if (!spmv_uses_lds(L) || L.blkcount != 0) return hipErrorInvalidValue;
+  if (L.n_owned == 0) return hipSuccess;
+  const size_t lds = size_t(SPMV_OWN_DIRECT && L.uown ? L.unmax : L.umax) * nf * sizeof(double);
+  const dim3 g = rows_grid(L.n_owned);
+  PNP_PAT_DISPATCH(nf, pat, {  // non-temporal value loads, as the LDS-staged SpMV's
+    hipLaunchKernelGGL((k_cheb_step_lds<NFc, PATc, 1>), g, dim3(kBlock), lds, s, L, vals, coef,
+                       step, last, r_in, r_out, p_old, p_new, z);
+  });
+  return hipGetLastError();
+}
+
+hipError_t launch_cheb_w0(int n_owned, int nf, const int *l2g, double *w, hipStream_t s) {
+  if (n_owned == 0) return hipSuccess;
+  hipLaunchKernelGGL(k_cheb_w0, rows_grid(n_owned), dim3(kBlock), 0, s, n_owned, nf, l2g, w);
   return hipGetLastError();
 }
 

@@ -7,7 +7,10 @@
 //                                                 ion current to current.dat)
 //
 // usage: pnp_main <config.cfg> [--refine k] [--mode stationary|instationary|md|pb] [--steps n]
-//                 [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec ...] [--amg-smoother s]
+//                 [--prec none|ssor|ssor_natural|jacobi|ilu0|amg|cheb] [--pb-prec ...]
+//                 [--amg-smoother s]
+//                 [--cheb-steps k]  (PNP_PREC_CHEBYSHEV, as --prec / --pb-prec / --amg-smoother cheb:
+//                                 block-Jacobi solves per application, 1 .. 16, default 3)
 //                 [--device d] [--out prefix]
 //                 [--matrix-free]  (PNP_OPT_MATRIX_FREE on every context: P1 only)
 //                 [--asm-full]  (PNP_OPT_ASM_REUSE_CONST = 0: every PnpOperator Jacobian assembly writes the
@@ -58,16 +61,18 @@ static int prec_of(const std::string &s) {
   if (s == "jacobi") return PNP_PREC_JACOBI;
   if (s == "ilu0") return PNP_PREC_ILU0;
   if (s == "amg") return PNP_PREC_AMG;  // level-0 smoother: --amg-smoother (PB: ssor, PNP: ilu0)
+  if (s == "cheb") return PNP_PREC_CHEBYSHEV;  // block-Jacobi solves per application: --cheb-steps
   throw pnp_gpu::Error(PNP_E_ARG, "unknown preconditioner " + s);
 }
 
 static void usage() {
   std::printf(
       "usage: pnp_main <config.cfg> [--refine k] [--mesh-scale s] [--mode stationary|instationary|md|pb]\n"
-      "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg] [--pb-prec p]\n"
+      "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg|cheb] [--pb-prec p]\n"
+      "                [--cheb-steps k]\n"
       "                [--device d] [--matrix-free] [--asm-full]\n"
       "                [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]\n"
-      "                [--amg-smoother ssor|ilu0|jacobi]\n"
+      "                [--amg-smoother ssor|ilu0|jacobi|cheb]\n"
       "                [--out prefix] [--md-reduction r] [--md-loop host|device] [--md-reuse 0|1]\n"
       "                [--linear-solver bcgs_ssork|bcgs_ssork_mc|bcgs_noprec|cg_noprec|cg_jacobi|cg_amg_ssor]\n"
       "                [--abs-limit a] [--dump-steps n1,n2,...] [--degree 1|2|3]\n"
@@ -232,6 +237,7 @@ int main(int argc, char **argv) {
   std::string method = "bicgstab";  // the Krylov method of the PNP phases (stationary / instationary)
   int restart = 0;                  // > 0: PNP_OPT_GMRES_RESTART
   int idr_s = 0;                    // > 0: PNP_OPT_IDR_S
+  int cheb_steps = 0;               // > 0: pnp_cheb_configure's steps (the other options default)
   for (int i = 2; i < argc; i++) {
     std::string a = argv[i];
     auto next = [&]() -> std::string {
@@ -256,6 +262,7 @@ int main(int argc, char **argv) {
     else if (a == "--method") method = next();
     else if (a == "--restart") restart = std::atoi(next().c_str());
     else if (a == "--idr-s") idr_s = std::atoi(next().c_str());
+    else if (a == "--cheb-steps") cheb_steps = std::atoi(next().c_str());
     else if (a == "--matrix-free") matrix_free = true;
     else if (a == "--asm-full") asm_full = true;
     else if (a == "--reference-solvers") {
@@ -316,6 +323,10 @@ int main(int argc, char **argv) {
     // operator applications computed from the linearisation state instead of the assembled matrix
     if (matrix_free) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_MATRIX_FREE, 1), ctx.get());
     if (asm_full) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_ASM_REUSE_CONST, 0), ctx.get());
+    if (cheb_steps != 0) {
+      const pnp_cheb_opts co{cheb_steps, 10.0, 20, 1.1, 0.0};
+      pnp_gpu::check(pnp_cheb_configure(ctx.get(), &co), ctx.get());
+    }
     const int newton_verbosity = rank == 0 ? (ref_order ? 2 : 1) : 0;
     int nv = ctx.nv();  // DOF nodes of the P_degree space
     if (rank == 0)

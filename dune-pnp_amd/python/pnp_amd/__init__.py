@@ -33,7 +33,8 @@ HEADER = os.path.join(REPO_ROOT, "include", "pnp_capi.h")
 OK, E_ARG, E_HIP, E_RCCL, E_BREAKDOWN, E_NOT_CONVERGED, E_IO, E_MESH, E_STATE = \
     0, -1, -2, -3, -4, -5, -6, -7, -8
 OP_PNP, OP_PNP_IMPLICIT_EULER, OP_PB, OP_DIFF, OP_DIFF_IMPLICIT_EULER, OP_POISSON = range(6)
-PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL = range(6)
+(PREC_NONE, PREC_SSOR, PREC_ILU0, PREC_JACOBI, PREC_AMG, PREC_SSOR_NATURAL,
+ PREC_CHEBYSHEV) = range(7)
 METHOD_BICGSTAB, METHOD_CG, METHOD_GMRES, METHOD_FGMRES, METHOD_IDR = 0, 1, 2, 3, 4
 (OPT_ILU_F32, OPT_ILU_FUSED_FACTOR, OPT_JAC_FD, OPT_BICG_TWORED, OPT_AMG_FALLBACK,
  OPT_GRAPH, OPT_SEQ_ORDER, OPT_ILU_FLOW, OPT_NAT_FLOW, OPT_ILU_RETRY,
@@ -47,7 +48,8 @@ ROW_FLAG_LOAD = 8  # PNP_ROW_FLAG_LOAD
 DEVICE_PTRS, JAC_FD = 1, 2
 CREATE_ABSORB_THIN_COLOR = 1
 PREC_BY_NAME = {"none": PREC_NONE, "nonprec": PREC_NONE, "ssor": PREC_SSOR, "ilu0": PREC_ILU0,
-                "jacobi": PREC_JACOBI, "amg": PREC_AMG, "ssor_natural": PREC_SSOR_NATURAL}
+                "jacobi": PREC_JACOBI, "amg": PREC_AMG, "ssor_natural": PREC_SSOR_NATURAL,
+                "cheb": PREC_CHEBYSHEV}
 MAX_SURFACES = 64
 
 
@@ -224,6 +226,17 @@ class _AmgOpts(C.Structure):
 class _AmgStats(C.Structure):
     _fields_ = [("levels", C.c_int32), ("smoother", C.c_int32), ("rows", C.c_int32 * 16),
                 ("blocks", C.c_int64 * 16), ("omega", C.c_double)]
+
+
+class _ChebOpts(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("eig_ratio", C.c_double), ("eig_iters", C.c_int32),
+                ("eig_boost", C.c_double), ("lambda_max", C.c_double)]
+
+
+class _ChebStats(C.Structure):
+    _fields_ = [("steps", C.c_int32), ("lambda_est", C.c_double), ("lambda_max", C.c_double),
+                ("lambda_min", C.c_double), ("applies", C.c_int64), ("estimates", C.c_int64),
+                ("fused_steps", C.c_int64), ("unfused_steps", C.c_int64)]
 
 
 class _NewtonOpts(C.Structure):
@@ -725,6 +738,21 @@ class Context:
         o = _AmgOpts(int(smoother), int(coarse_target), int(max_levels), float(omega),
                      int(coarse_sweeps), int(level0_presmooth))
         self._ck(lib().pnp_amg_configure(self.h, C.byref(o)))
+
+    def cheb_configure(self, steps=3, eig_ratio=10.0, eig_iters=20, eig_boost=1.1,
+                       lambda_max=0.0):
+        """Options of PREC_CHEBYSHEV (pnp_cheb_configure): `steps` block-Jacobi solves per
+        application; lambda_max > 0 sets the upper bound, 0 estimates it (eig_iters power-iteration
+        steps, times eig_boost); lambda_min = lambda_max / eig_ratio."""
+        o = _ChebOpts(int(steps), float(eig_ratio), int(eig_iters), float(eig_boost),
+                      float(lambda_max))
+        self._ck(lib().pnp_cheb_configure(self.h, C.byref(o)))
+
+    def cheb_info(self):
+        """pnp_cheb_info: the configured steps, the estimate and bounds last used, the counters."""
+        st = _ChebStats()
+        self._ck(lib().pnp_cheb_info(self.h, C.byref(st)))
+        return {k: getattr(st, k) for k, _ in _ChebStats._fields_}
 
     def amg_info(self):
         st = _AmgStats()

@@ -304,7 +304,16 @@ enum { PNP_PREC_NONE = 0, PNP_PREC_SSOR = 1, PNP_PREC_ILU0 = 2, PNP_PREC_JACOBI 
         * src/stationary_pnp_from_pb.hh:168-169), so iteration counts compare with the reference's.
         * Level-scheduled on the GPU (one launch per dependency level, ~100-300 levels): a parity
         * mode, slower than the multicolour PNP_PREC_SSOR.  Block-Jacobi across ranks. */
-       PNP_PREC_SSOR_NATURAL = 5 };
+       PNP_PREC_SSOR_NATURAL = 5,
+       /* Chebyshev polynomial in the vertex-block-Jacobi-scaled operator D^-1 A, D the nf x nf
+        * diagonal blocks (Dirichlet rows identity): `steps` block-Jacobi solves and steps - 1
+        * operator applications per application, one launch each, no colours, no factorisation, no
+        * split storage.  The operator is the global one (a halo exchange per step), so the
+        * preconditioner does not depend on the rank count; with PNP_OPT_MATRIX_FREE it applies the
+        * matrix-free operator and never assembles the SELL values.  A fixed linear operator: every
+        * method takes it (symmetric for symmetric A, so CG may use it).  steps = 1 is vertex-block
+        * Jacobi.  See pnp_cheb_configure; DESIGN.md 4.13.  Not in reference-order mode. */
+       PNP_PREC_CHEBYSHEV = 6 };
 enum { PNP_METHOD_BICGSTAB = 0, PNP_METHOD_CG = 1,
        /* Restarted GMRES(m), right-preconditioned (x = x0 + M^-1 V y): the monitored norm is the
         * true residual's, so `reduction` means what it means for the other methods.  m =
@@ -368,7 +377,9 @@ int pnp_prec_apply(pnp_ctx *ctx, int32_t prec, const double *d, double *v);
  * dense direct solve on the coarsest.  Rank-local (block-Jacobi across ranks, like the sweeps).
  * With PNP_METHOD_CG and smoother SSOR this is CG_AMG_SSOR; it also preconditions BiCGSTAB. */
 typedef struct {
-  int32_t smoother;       /* level-0 smoother: PNP_PREC_SSOR (default), PNP_PREC_ILU0, PNP_PREC_JACOBI */
+  int32_t smoother;       /* level-0 smoother: PNP_PREC_SSOR (default), PNP_PREC_ILU0, PNP_PREC_JACOBI,
+                             PNP_PREC_SSOR_NATURAL, PNP_PREC_CHEBYSHEV (rank-local inside the
+                             cycle, with the context's one pair of bounds) */
   int32_t coarse_target;  /* coarsen until at most this many vertex blocks (1..1024, default 1024:
                              the coarsest level is inverted densely, rocSOLVER getrf/getri,
                              <= 3072 unknowns) */
@@ -393,6 +404,38 @@ int pnp_amg_info(pnp_ctx *ctx, pnp_amg_stats *stats);
 /* aggregate map of level -> level+1 (test hook): level 0 indexed by global vertex (-1: not owned
  * by this rank, agg sized nv), coarser levels by row */
 int pnp_amg_aggregates(pnp_ctx *ctx, int32_t level, int32_t *agg);
+
+/* ---- Chebyshev polynomial preconditioner (PNP_PREC_CHEBYSHEV) ----------------------------------
+ * z = q(D^-1 A) D^-1 d with q the degree steps-1 Chebyshev polynomial for the interval
+ * [lambda_min, lambda_max]: lambda_max = eig_boost x lambda_est, or the caller's lambda_max if
+ * > 0; lambda_min = lambda_max / eig_ratio.  lambda_est = |w_m| / |w_{m-1}| of m = eig_iters
+ * unnormalised power-iteration steps w_j = D^-1 A w_{j-1} from a counter-based start vector (by
+ * global node and field: independent of layout and partition), run once per stored Jacobian at
+ * the first use after it.  steps = 1 needs no bounds and runs no estimate.
+ * NULL: the defaults, steps 3, eig_ratio 10, eig_iters 20, eig_boost 1.1, lambda_max 0 (estimate).
+ * PNP_E_ARG outside steps 1 .. 16, eig_ratio > 1, eig_iters 1 .. 100, eig_boost >= 1,
+ * lambda_max >= 0.  The call drops the estimate and every captured graph. */
+typedef struct {
+  int32_t steps;
+  double eig_ratio;
+  int32_t eig_iters;
+  double eig_boost;
+  double lambda_max;
+} pnp_cheb_opts;
+int pnp_cheb_configure(pnp_ctx *ctx, const pnp_cheb_opts *opts);
+/* steps: the configured count.  lambda_*: the estimate and the bounds last used (0 before the
+ * first use, and with steps 1; lambda_est 0 with a caller's lambda_max).  Counters since the
+ * context was created: applies = preconditioner applications, estimates = power iterations run,
+ * fused_steps / unfused_steps = steps i >= 1 run as the one-launch fused step / as an operator
+ * application followed by the update kernel (more than one rank, matrix-free with stale values,
+ * layouts without the SpMV's LDS lists, or the environment variable PNP_CHEB_FUSED=0, read once
+ * per process).  An application captured into a replayed graph counts once. */
+typedef struct {
+  int32_t steps;
+  double lambda_est, lambda_max, lambda_min;
+  int64_t applies, estimates, fused_steps, unfused_steps;
+} pnp_cheb_stats;
+int pnp_cheb_info(pnp_ctx *ctx, pnp_cheb_stats *stats);
 
 /* ---- context options ------------------------------------------------------------------------ */
 enum {
@@ -488,9 +531,9 @@ enum {
    * multiplies each finished block by its neighbour's z instead of storing it.  The SELL values
    * are assembled, at the recorded point, only when something reads them: the SSOR, ILU(0), AMG
    * and natural-order SSOR set-up, pnp_jacobian_export, pnp_jacobian_csr_device.  So every
-   * preconditioner, export and view works as before, and solves with PNP_PREC_NONE or
-   * PNP_PREC_JACOBI (which takes the diagonal blocks from a walk of its own), Newton included,
-   * never write the matrix (pnp_matfree_info counts).  Ignored, with the assembled path taken,
+   * preconditioner, export and view works as before, and solves with PNP_PREC_NONE,
+   * PNP_PREC_JACOBI or PNP_PREC_CHEBYSHEV (which take the diagonal blocks from a walk of their
+   * own), Newton included, never write the matrix (pnp_matfree_info counts).  Ignored, with the assembled path taken,
    * for forward-difference Jacobians (PNP_OPT_JAC_FD, PNP_JAC_FD) and in reference-order mode
    * (PNP_OPT_SEQ_ORDER).  On a P_k context of degree > 1 setting 1 returns PNP_E_STATE.  Turning
    * it off assembles the values of the current Jacobian if nobody had needed them yet.
