@@ -907,7 +907,7 @@ int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
   D.ok = false;
   const int nc = int(L.color_ptr.size()) - 1;
   const std::vector<int> &cp = L.color_ptr;
-  if (!dl.lsx_ptr || nc < 2 || h_posrowL.empty()) return PNP_OK;
+  if (!dl.lsx_ptr || nc < 2 || hl.posrowL.empty()) return PNP_OK;
   std::vector<int> nb(nc), blk0(nc + 1, 0);
   for (int c = 0; c < nc; c++) {
     nb[c] = (cp[c + 1] - cp[c] + 255) / 256;
@@ -938,8 +938,8 @@ int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
     const int c = stages[s].second, kind = stages[s].first;
     for (int p = cp[c]; p < cp[c + 1]; p++) {
       const int u = F.unit0[s] + (p - cp[c]) / 256;
-      if (kind != 1) fwdu[h_posrowL[p]] = u;
-      if (kind != 0) bwdu[h_posrowU[p]] = u;
+      if (kind != 1) fwdu[hl.posrowL[p]] = u;
+      if (kind != 0) bwdu[hl.posrowU[p]] = u;
     }
   }
   // readers[r]: forward / last units whose L list holds row r (CSR)
@@ -950,8 +950,8 @@ int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
       if (F.kind[s] == 1) continue;
       for (int u = F.unit0[s]; u < F.unit0[s + 1]; u++) {
         const int b = lblock(s, u);
-        for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++) {
-          const int j = h_lsx_list[k];
+        for (int k = hl.lsx_ptr[b]; k < hl.lsx_ptr[b + 1]; k++) {
+          const int j = hl.lsx_list[k];
           if (pass == 0)
             rptr[j + 1]++;
           else
@@ -974,14 +974,14 @@ int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
       const int b = lblock(s, u);
       dep.clear();
       if (F.kind[s] != 1) {
-        for (int k = h_lsx_ptr[b]; k < h_lsx_ptr[b + 1]; k++)
-          if (fwdu[h_lsx_list[k]] >= 0) dep.push_back(fwdu[h_lsx_list[k]]);
+        for (int k = hl.lsx_ptr[b]; k < hl.lsx_ptr[b + 1]; k++)
+          if (fwdu[hl.lsx_list[k]] >= 0) dep.push_back(fwdu[hl.lsx_list[k]]);
       } else {
-        for (int k = h_usx_ptr[b]; k < h_usx_ptr[b + 1]; k++)
-          if (bwdu[h_usx_list[k]] >= 0) dep.push_back(bwdu[h_usx_list[k]]);
+        for (int k = hl.usx_ptr[b]; k < hl.usx_ptr[b + 1]; k++)
+          if (bwdu[hl.usx_list[k]] >= 0) dep.push_back(bwdu[hl.usx_list[k]]);
         const int p0 = cp[c] + 256 * (u - F.unit0[s]), p1 = std::min(cp[c + 1], p0 + 256);
         for (int p = p0; p < p1; p++) {
-          const int r = h_posrowU[p];
+          const int r = hl.posrowU[p];
           if (fwdu[r] >= 0) dep.push_back(fwdu[r]);
           for (int k = rptr[r]; k < rptr[r + 1]; k++) dep.push_back(rdr[k]);
         }
@@ -995,15 +995,9 @@ int pnp_ctx::ilu_flow_build(int c_first, IluFlowDev &D) {
     }
   }
   if (dlist.empty()) dlist.push_back(0);
-  auto upv = [&](auto &buf, const auto &vec, const char *what) -> int {
-    hipError_t e2 = buf.alloc(vec.size());
-    if (e2 == hipSuccess)
-      e2 = hipMemcpy(buf.p, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice);
-    return e2 == hipSuccess ? PNP_OK : hipfail(e2, what);
-  };
   int rc;
-  if ((rc = upv(D.dep_ptr, dptr, "ILU(0) dataflow deps")) ||
-      (rc = upv(D.dep_list, dlist, "ILU(0) dataflow deps")))
+  if ((rc = upload(D.dep_ptr, dptr, "ILU(0) dataflow deps")) ||  // neither is empty
+      (rc = upload(D.dep_list, dlist, "ILU(0) dataflow deps")))
     return rc;
   hipError_t e = D.flags.alloc(size_t(nu + 1 + 3) & ~size_t(3));
   if (e == hipSuccess && !ilu_flow_abort.p) {
@@ -1231,10 +1225,7 @@ int pnp_ctx::pk_build() {
     const int nblk = (L.n_owned + 255) / 256;
     std::vector<int> order(nblk), blen(nblk, 0);
     for (int b = 0; b < nblk; b++) order[b] = b;
-    if (dl.blkmap && nblk > 0) {
-      e = hipMemcpy(order.data(), dl.blkmap, sizeof(int) * nblk, hipMemcpyDeviceToHost);
-      if (e != hipSuccess) return hipfail(e, "blkmap");
-    }
+    if (dl.blkmap && nblk > 0) order = hl.blkmap;
     for (int r = 0; r < L.n_owned; r++)
       blen[r / 256] = std::max(blen[r / 256], pnp::meta_len(L.rowmeta[r]));
     std::vector<int> srt(blen);
@@ -1905,6 +1896,234 @@ extern "C" int pnp_create(const pnp_mesh *mesh, const pnp_params *params, int32_
   return pnp_create_pk(mesh, params, 1, device, comm, out);
 }
 
+// mesh, parameters, rank and the host front half (layout_derive.cc): nothing here needs a device,
+// and every rank fails here alike, before any collective
+int pnp_ctx::create_host(const pnp_mesh *mesh_in, const pnp_params *pp, int degree_in,
+                         const pnp_comm *comm_in) {
+  std::string e;
+  if (!mesh_from_view(mesh_in, mesh, e)) return fail(PNP_E_MESH, e);
+  for (int s = 0; s < mesh.nb; s++)
+    if (mesh.bgroup[s] < 0 || mesh.bgroup[s] >= pp->n_surfaces)
+      return fail(PNP_E_ARG, "boundary segment " + std::to_string(s) + " has physical group " +
+                                 std::to_string(mesh.bgroup[s]) + " but only " +
+                                 std::to_string(pp->n_surfaces) + " surfaces are configured");
+  params_from(pp, params);
+  if (comm_in && comm_in->size > 1) {
+    rank = comm_in->rank;
+    nranks = comm_in->size;
+    if (comm_in->rank < 0 || comm_in->rank >= comm_in->size ||
+        (!comm_in->rccl_unique_id && !comm_in->local_group && !comm_in->host))
+      return fail(PNP_E_ARG,
+                  "invalid pnp_comm (need an RCCL unique id, a local group or a host transport)");
+  }
+  degree = degree_in;
+  if (!pnp::build_host_layout(mesh, degree, rank, nranks, tmesh, pks, fans, L, e))
+    return fail(PNP_E_MESH, e);
+  return PNP_OK;
+}
+
+int pnp_ctx::create_device(int device_in, const pnp_comm *comm_in) {
+  device = device_in;
+  hipError_t e = hipSetDevice(device);
+  if (e != hipSuccess) return hipfail(e, "hipSetDevice");
+  e = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
+  if (e != hipSuccess) return hipfail(e, "hipStreamCreate");
+  if (comm_in && comm_in->rccl_unique_id && (nranks > 1 || comm_in->size == 1)) {
+    ncclUniqueId id;
+    std::memcpy(&id, comm_in->rccl_unique_id, sizeof id);
+    ncclResult_t nr = ncclCommInitRank(&comm, nranks, id, rank);
+    if (nr != ncclSuccess)
+      return fail(PNP_E_RCCL, std::string("ncclCommInitRank failed: ") + ncclGetErrorString(nr) +
+                                  " (" + ncclGetLastError(nullptr) + ")");
+  }
+  dist = nranks > 1 || comm != nullptr;
+  return PNP_OK;
+}
+
+// every array of the layout and of its derived lists (layout_derive.h) to the device, each
+// DevLayout pointer set beside its upload.  Lists that are "not usable" leave their pointers null
+int pnp_ctx::upload_layout(const pnp::DerivedLayout &D, const pnp::LayoutKnobs &K) {
+  const int nloc = L.n_owned + L.n_ghost;
+  std::vector<double> xy(2 * size_t(nloc));
+  for (int i = 0; i < nloc; i++) {
+    xy[2 * size_t(i)] = mesh.xy[2 * size_t(L.l2g[i])];
+    xy[2 * size_t(i) + 1] = mesh.xy[2 * size_t(L.l2g[i]) + 1];
+  }
+  int rc;
+  auto up = [&](auto &buf, const auto &vec, auto &dlp, const char *what) {
+    const int r = upload(buf, vec, what);
+    dlp = buf.p;
+    return r;
+  };
+  const pnp::SplitLayout &S = D.split;
+  if ((rc = up(d_lperm, S.lperm, dl.lperm, "lperm")) || (rc = up(d_uperm, S.uperm, dl.uperm, "uperm")) ||
+      (rc = up(d_lpinv, S.lpinv, dl.lpinv, "lpinv")) || (rc = up(d_upinv, S.upinv, dl.upinv, "upinv")) ||
+      (rc = up(d_llen, S.llen, dl.llen, "llen")) || (rc = up(d_ulen, S.ulen, dl.ulen, "ulen")) ||
+      (rc = up(d_ldl, S.ldl, dl.ldl, "ldl")))
+    return rc;
+  if ((rc = up(d_lchunk_len, S.lchunk_len, dl.lchunk_len, "lchunk_len")) ||
+      (rc = up(d_lchunk_off, S.lchunk_off, dl.lchunk_off, "lchunk_off")) ||
+      (rc = up(d_lcolidx, S.lcolidx, dl.lcolidx, "lcolidx")) || (rc = upload(d_lsrc, S.lsrc, "lsrc")) ||
+      (rc = up(d_uchunk_len, S.uchunk_len, dl.uchunk_len, "uchunk_len")) ||
+      (rc = up(d_uchunk_off, S.uchunk_off, dl.uchunk_off, "uchunk_off")) ||
+      (rc = up(d_ucolidx, S.ucolidx, dl.ucolidx, "ucolidx")) || (rc = upload(d_usrc, S.usrc, "usrc")))
+    return rc;
+  if (const pnp::SweepLists &X = D.sweep; X.usable) {
+    if ((rc = up(d_lsx_ptr, X.lptr, dl.lsx_ptr, "lsx ptr")) ||
+        (rc = up(d_lsx_list, X.llist, dl.lsx_list, "lsx list")) ||
+        (rc = up(d_lsx_idx, X.lidx, dl.lsx_idx, "lsx idx")) ||
+        (rc = up(d_usx_ptr, X.uptr, dl.usx_ptr, "usx ptr")) ||
+        (rc = up(d_usx_list, X.ulist, dl.usx_list, "usx list")) ||
+        (rc = up(d_usx_idx, X.uidx, dl.usx_idx, "usx idx")))
+      return rc;
+    dl.sx_max = X.sx_max;
+    ilu_flow[0].built = ilu_flow[1].built = false;
+  }
+  if ((rc = upload(d_rowoff, D.rows.rowoff, "rowoff")) || (rc = upload(d_rowcol, D.rows.rowcol, "rowcol")))
+    return rc;
+  if (!D.blkmap.empty() && (rc = up(d_blkmap, D.blkmap, dl.blkmap, "blkmap"))) return rc;
+  fseg_group = D.flux.group;
+  if ((rc = upload(d_fseg, D.flux.segs, "flux segments"))) return rc;
+  if ((rc = up(d_chunk_len, L.chunk_len, dl.chunk_len, "chunk_len")) ||
+      (rc = up(d_chunk_off, L.chunk_off, dl.chunk_off, "chunk_off")) ||
+      (rc = up(d_colidx, L.colidx, dl.colidx, "colidx")) ||
+      (rc = up(d_rowmeta, L.rowmeta, dl.rowmeta, "rowmeta")) || (rc = up(d_xy, xy, dl.xy, "xy")) ||
+      (rc = upload(d_l2g, L.l2g, "l2g")) || (rc = upload(d_send_idx, L.send_idx, "send_idx")) ||
+      (rc = up(d_color_idx, L.color_idx, dl.color_idx, "color_idx")) ||
+      (rc = up(d_rowcolor, L.rowcolor, dl.rowcolor, "rowcolor")))
+    return rc;
+  dl.xcd_remap = K.xcd_remap;
+  dl.n_owned = L.n_owned;
+  dl.n_local = nloc;
+  dl.nchunks = L.nchunks;
+  dl.max_slots = L.chunk_len.empty() ? 0 : *std::max_element(L.chunk_len.begin(), L.chunk_len.end());
+  dl.ncolors = int(L.color_ptr.size()) - 1;
+  if (const pnp::SpmvLists &U = D.spmv; U.usable) {
+    if ((rc = up(d_uptr, U.uptr, dl.uptr, "uptr")) || (rc = up(d_ulist, U.ulist, dl.ulist, "ulist")) ||
+        (rc = up(d_lidx, U.lidx, dl.lidx, "lidx")) || (rc = up(d_uown, U.uown, dl.uown, "uown")))
+      return rc;
+    dl.umax = U.umax;
+    dl.unmax = U.unmax;
+  }
+  if (dist && D.halo.usable) {  // halo-overlapped SpMV (sub_layout)
+    if ((rc = upload(d_blk_int, D.halo.interior, "interior blocks")) ||
+        (rc = upload(d_blk_bnd, D.halo.boundary, "boundary blocks")))
+      return rc;
+    n_blk_int = int(D.halo.interior.size());
+    n_blk_bnd = int(D.halo.boundary.size());
+    split_spmv = true;
+  }
+  return PNP_OK;
+}
+
+// the matrix values, the solver vectors and the scratch buffers, zeroed
+int pnp_ctx::alloc_vectors() {
+  const int nloc = L.n_owned + L.n_ghost;
+  size_t nv3 = 3 * size_t(nloc);
+  int rc;
+  auto al = [&](auto &buf, size_t n, const char *what) -> int {
+    hipError_t e2 = buf.alloc(n);  // zeroed, and the zeroing finished (DBuf::alloc)
+    if (e2 != hipSuccess) return hipfail(e2, what);
+    return PNP_OK;
+  };
+  if ((rc = al(vals, size_t(L.nslots) * 8, "vals")) ||
+      (rc = al(lu, size_t(L.nslots) * 8, "lu")) ||
+      (rc = al(lvals, d_lsrc.n * 8, "lvals")) || (rc = al(uvals, d_usrc.n * 8, "uvals")) ||
+      (rc = al(tsgs, nv3, "sgs scratch")) || (rc = al(fluxx, nv3, "flux state")) ||
+      (rc = al(fluxout, 2 * fseg_group.size() + 2, "flux out")) ||
+      (rc = al(fluxred, 2 * 256, "flux reduce")) || (rc = al(x, nv3, "x")) ||
+      (rc = al(r, nv3, "r")) || (rc = al(rs, nv3, "rs")) || (rc = al(z, nv3, "z")) || (rc = al(rt, nv3, "rt")) ||
+      (rc = al(p, nv3, "p")) || (rc = al(v, nv3, "v")) || (rc = al(t, nv3, "t")) ||
+      (rc = al(y, nv3, "y")) || (rc = al(y2, nv3, "y2")) ||
+      (rc = al(ilu_y32buf, nv3, "ILU(0) intermediate")) || (rc = al(b, nv3, "b")) || (rc = al(prevu, nv3, "prevu")) ||
+      (rc = al(ext, 3 * size_t(mesh.nv), "ext")) ||
+      (rc = al(sendbuf, 3 * std::max<size_t>(1, L.send_idx.size()), "sendbuf")) ||
+      // up to 3 partials per workgroup (SpMV mode 4) / 2 (updates with <rt, s>)
+      (rc = al(partials,
+               3 * std::max<size_t>(size_t(pnp::blas_nparts(3LL * nloc)),
+                                    size_t(pnp::spmv_parts(L.n_owned))) + 64,
+               "partials")) ||
+      (rc = al(partials2,
+               2 * std::max<size_t>(size_t(pnp::blas_nparts(3LL * nloc)),
+                                    size_t(pnp::spmv_parts(L.n_owned))) + 64,
+               "partials2")) ||
+      (rc = al(S, 2, "scalars")) || (rc = al(redmw, pnp::kRedMwDoubles, "reduce ticket")) ||
+      (rc = al(dmask, 3 * size_t(L.n_owned), "dmask")) ||
+      (rc = al(rowflag, size_t(L.nchunks + 1) * pnp::kRows, "row flags")) ||
+      (rc = al(cvec, 3 * size_t(L.n_owned), "cvec")) || (rc = al(aux0, nloc, "aux0")) ||
+      (rc = al(aux1, nloc, "aux1")))
+    return rc;
+  hipError_t e = hipHostMalloc(&hS, 3 * sizeof(pnp::Scalars));
+  if (e != hipSuccess) return hipfail(e, "hipHostMalloc");
+  return PNP_OK;
+}
+
+// the RCCL halo of the overlapped SpMV runs on a stream of its own
+int pnp_ctx::create_halo_stream(const pnp_comm *comm_in) {
+  if (!split_spmv || !comm_in->rccl_unique_id) return PNP_OK;
+  hipError_t e;
+  if ((e = hipStreamCreateWithFlags(&cstream, hipStreamNonBlocking)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&ev_ready, hipEventDisableTiming)) != hipSuccess ||
+      (e = hipEventCreateWithFlags(&ev_halo, hipEventDisableTiming)) != hipSuccess)
+    return hipfail(e, "halo stream");
+  return PNP_OK;
+}
+
+int pnp_ctx::create_host_transport(const pnp_comm *comm_in) {
+  if (!(nranks > 1 && !comm_in->rccl_unique_id && !comm_in->local_group)) return PNP_OK;
+  if (!comm_in->host->exchange || !comm_in->host->allreduce_sum)
+    return fail(PNP_E_ARG, "pnp_host_transport: exchange and allreduce_sum are required");
+  ht = *comm_in->host;
+  const size_t ns = 3 * std::max<size_t>(1, L.send_idx.size());
+  const size_t nr = 3 * std::max<size_t>(1, size_t(L.n_ghost));
+  hipError_t e;
+  if ((e = hipHostMalloc(&h_send, sizeof(double) * ns)) != hipSuccess ||
+      (e = hipHostMalloc(&h_recv, sizeof(double) * nr)) != hipSuccess)
+    return hipfail(e, "host transport staging");
+  return PNP_OK;
+}
+
+// join the in-process group; the barrier: all ranks created before any collective
+int pnp_ctx::join_local_group(const pnp_comm *comm_in) {
+  if (!(nranks > 1 && !comm_in->rccl_unique_id && comm_in->local_group)) return PNP_OK;
+  std::shared_ptr<LocalGroup> g;
+  {
+    std::lock_guard<std::mutex> lk(g_groups_m);
+    auto &slot = g_groups[comm_in->local_group];
+    if (!slot || slot->size != nranks) {
+      slot = std::make_shared<LocalGroup>();
+      slot->size = nranks;
+      slot->members.assign(nranks, nullptr);
+      slot->host.assign(nranks, {});
+    }
+    g = slot;
+    if (g->members[rank]) return fail(PNP_E_ARG, "rank already present in local group");
+    g->members[rank] = this;
+  }
+  lg = g;
+  g->barrier();
+  return PNP_OK;
+}
+
+// The steps of pnp_create_pk after its argument checks.  Everything up to create_device fails on
+// every rank alike before ncclCommInitRank; everything before join_local_group before its barrier
+int pnp_ctx::create(const pnp_mesh *mesh_in, const pnp_params *pp, int degree_in, int device_in,
+                    const pnp_comm *comm_in) {
+  int rc;
+  if ((rc = create_host(mesh_in, pp, degree_in, comm_in)) || (rc = create_device(device_in, comm_in)))
+    return rc;
+  const pnp::LayoutKnobs knobs = pnp::LayoutKnobs::from_env();
+  pnp::DerivedLayout D;
+  std::string e;
+  if (!pnp::derive_layout(mesh, L, knobs, D, e)) return fail(PNP_E_MESH, e);
+  if ((rc = upload_layout(D, knobs)) || (rc = alloc_vectors()) || (rc = create_halo_stream(comm_in)))
+    return rc;
+  hl = pnp::keep_layout(std::move(D));
+  if (degree > 1 && (rc = pk_build())) return rc;
+  if ((rc = create_host_transport(comm_in))) return rc;
+  return join_local_group(comm_in);
+}
+
 extern "C" int pnp_create_pk(const pnp_mesh *mesh, const pnp_params *params, int32_t degree,
                              int32_t device, const pnp_comm *comm, pnp_ctx **out) {
   if (degree < 1 || degree > 3) {
@@ -1920,591 +2139,14 @@ extern "C" int pnp_create_pk(const pnp_mesh *mesh, const pnp_params *params, int
     return PNP_E_ARG;
   }
   auto c = std::make_unique<pnp_ctx>();
-  std::string err;
-  if (!mesh_from_view(mesh, c->mesh, err)) {
-    g_err = err;
-    return PNP_E_MESH;
-  }
-  for (int s = 0; s < c->mesh.nb; s++)
-    if (c->mesh.bgroup[s] < 0 || c->mesh.bgroup[s] >= params->n_surfaces) {
-      g_err = "boundary segment " + std::to_string(s) + " has physical group " +
-              std::to_string(c->mesh.bgroup[s]) + " but only " +
-              std::to_string(params->n_surfaces) + " surfaces are configured";
-      return PNP_E_ARG;
-    }
-  params_from(params, c->params);
-  if (comm && comm->size > 1) {
-    c->rank = comm->rank;
-    c->nranks = comm->size;
-    if (comm->rank < 0 || comm->rank >= comm->size ||
-        (!comm->rccl_unique_id && !comm->local_group && !comm->host)) {
-      g_err = "invalid pnp_comm (need an RCCL unique id, a local group or a host transport)";
-      return PNP_E_ARG;
-    }
-  }
-  c->degree = degree;
-  if (degree > 1) {  // the layout is built on the node graph of the P_k space
-    if (!pnp::validate(c->mesh, err) || !pnp::build_pk_space(c->mesh, degree, c->pks, err)) {
-      g_err = err;
-      return PNP_E_MESH;
-    }
-    c->tmesh = std::move(c->mesh);
-    c->mesh = pnp::pk_node_mesh(c->pks);
-    if (!pnp::pk_adjacency(c->tmesh, c->pks, c->fans, err)) {
-      g_err = err;
-      return PNP_E_MESH;
-    }
-  } else if (!pnp::build_fans(c->mesh, c->fans, err)) {
-    g_err = err;
-    return PNP_E_MESH;
-  }
-  std::vector<int> part;
-  pnp::rcb_partition(c->mesh, c->nranks, part);
-  {  // every rank computes the same partition: all of them fail here, before any collective or
-     // group barrier, when one part is empty (more ranks than vertices)
-    std::vector<int> cnt(c->nranks, 0);
-    for (int p : part) cnt[p]++;
-    for (int r = 0; r < c->nranks; r++)
-      if (cnt[r] == 0) {
-        g_err = "partition: rank " + std::to_string(r) + " of " + std::to_string(c->nranks) +
-                " owns no vertices (the mesh has " + std::to_string(c->mesh.nv) + ")";
-        return PNP_E_MESH;
-      }
-  }
-  if (!pnp::build_local_layout(c->mesh, c->fans, part, c->rank, c->nranks, c->L, err)) {
-    g_err = err;
-    return PNP_E_MESH;
-  }
-  c->device = device;
-  hipError_t e = hipSetDevice(device);
-  if (e != hipSuccess) {
-    g_err = std::string("hipSetDevice: ") + hipGetErrorString(e);
-    return PNP_E_HIP;
-  }
-  e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-  if (e != hipSuccess) {
-    g_err = std::string("hipStreamCreate: ") + hipGetErrorString(e);
-    return PNP_E_HIP;
-  }
-  if (comm && comm->rccl_unique_id && (c->nranks > 1 || comm->size == 1)) {
-    ncclUniqueId id;
-    std::memcpy(&id, comm->rccl_unique_id, sizeof id);
-    ncclResult_t nr = ncclCommInitRank(&c->comm, c->nranks, id, c->rank);
-    if (nr != ncclSuccess) {
-      g_err = std::string("ncclCommInitRank failed: ") + ncclGetErrorString(nr) + " (" +
-              ncclGetLastError(nullptr) + ")";
-      return PNP_E_RCCL;
-    }
-  }
-  c->dist = c->nranks > 1 || c->comm != nullptr;
-  pnp::LocalLayout &L = c->L;
-  int nloc = L.n_owned + L.n_ghost;
-  std::vector<double> xy(2 * size_t(nloc));
-  for (int i = 0; i < nloc; i++) {
-    xy[2 * size_t(i)] = c->mesh.xy[2 * size_t(L.l2g[i])];
-    xy[2 * size_t(i) + 1] = c->mesh.xy[2 * size_t(L.l2g[i]) + 1];
-  }
-  pnp_ctx *cp = c.get();
-  auto up = [&](auto &buf, const auto &vec, const char *what) -> int {
-    hipError_t e2 = buf.alloc(vec.size());
-    if (e2 == hipSuccess && !vec.empty())
-      e2 = hipMemcpy(buf.p, vec.data(), sizeof(vec[0]) * vec.size(), hipMemcpyHostToDevice);
-    if (e2 != hipSuccess) return cp->hipfail(e2, what);
-    return PNP_OK;
-  };
-  int rc;
-  // triangular split of the owned-column pattern (DevLayout l*/u*).  Lane order (PNP_SPLIT_SORT,
-  // default on): inside each 64-row chunk, and inside each colour's segment of it, the rows are
-  // stored longest-first in each of L and U, so a slot plane's padding is a tail of lanes that
-  // issue no loads (config 3: 17.8 % of the split slots are padding); position p = 64 ch + lane
-  // holds row 64 ch + lperm[p] in L and 64 ch + uperm[p] in U.  A row's own arithmetic and slot
-  // order are unchanged, so every result is bitwise the identity order's.
-  const int no = L.n_owned, npos = 64 * L.nchunks;
-  std::vector<int> nlr(npos, 0), nur(npos, 1);
-  for (int row = 0; row < no; row++) {
-    const int ch = row / 64, ln = row % 64, len = int(L.rowmeta[row] & 63);
-    for (int sl = 1; sl < len; sl++) {
-      const int j = L.colidx[size_t(L.chunk_off[ch]) + 64 * sl + ln];
-      // ghost and same-colour columns are outside the sweeps (mesh.cc absorb_top)
-      if (j >= no || j == row || L.rowcolor[j] == L.rowcolor[row]) continue;
-      (j < row ? nlr[row] : nur[row])++;
-    }
-  }
-  std::vector<uint8_t> lperm(npos), uperm(npos), lpinv(npos), upinv(npos), llen8(npos, 0),
-      ulen8(npos, 0), ldl(npos);
-  const bool sort_lanes = [] {
-    const char *e = getenv("PNP_SPLIT_SORT");
-    return !(e && e[0] == '0');
-  }();
-  for (int ch = 0; ch < L.nchunks; ch++) {
-    for (int ln = 0; ln < 64; ln++) lperm[64 * ch + ln] = uperm[64 * ch + ln] = uint8_t(ln);
-    for (int a0 = 64 * ch; a0 < std::min(no, 64 * ch + 64);) {  // colour segments
-      int a1 = a0 + 1;
-      while (a1 < std::min(no, 64 * ch + 64) && L.rowcolor[a1] == L.rowcolor[a0]) a1++;
-      if (sort_lanes) {
-        std::vector<int> ord(a1 - a0);
-        for (int k = 0; k < a1 - a0; k++) ord[k] = a0 + k;
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return nlr[x] > nlr[y]; });
-        for (int k = 0; k < a1 - a0; k++) lperm[a0 + k] = uint8_t(ord[k] - 64 * ch);
-        for (int k = 0; k < a1 - a0; k++) ord[k] = a0 + k;
-        std::stable_sort(ord.begin(), ord.end(), [&](int x, int y) { return nur[x] > nur[y]; });
-        for (int k = 0; k < a1 - a0; k++) uperm[a0 + k] = uint8_t(ord[k] - 64 * ch);
-      }
-      a0 = a1;
-    }
-  }
-  auto rowL = [&](int pos) { return 64 * (pos / 64) + lperm[pos]; };
-  auto rowU = [&](int pos) { return 64 * (pos / 64) + uperm[pos]; };
-  for (int pos = 0; pos < npos; pos++) {
-    lpinv[rowL(pos)] = uint8_t(pos % 64);
-    upinv[rowU(pos)] = uint8_t(pos % 64);
-  }
-  c->lslots_live = c->uslots_live = 0;
-  for (int pos = 0; pos < npos; pos++) {
-    llen8[pos] = uint8_t(nlr[rowL(pos)]);
-    ulen8[pos] = uint8_t(nur[rowU(pos)]);
-    ldl[pos] = upinv[rowL(pos)];
-    if (rowL(pos) < no) c->lslots_live += nlr[rowL(pos)];
-    if (rowU(pos) < no) c->uslots_live += nur[rowU(pos)];
-  }
-  std::vector<int> lcl(L.nchunks), lco(L.nchunks + 1, 0), ucl(L.nchunks), uco(L.nchunks + 1, 0);
-  for (int ch = 0; ch < L.nchunks; ch++) {
-    int ml = 0, mu = 1;
-    for (int row = 64 * ch; row < std::min(no, 64 * ch + 64); row++) {
-      ml = std::max(ml, nlr[row]);
-      mu = std::max(mu, nur[row]);
-    }
-    lcl[ch] = ml;
-    ucl[ch] = mu;
-    lco[ch + 1] = lco[ch] + 64 * ml;
-    uco[ch + 1] = uco[ch] + 64 * mu;
-  }
-  std::vector<int> lcol(lco[L.nchunks]), lsrc(lco[L.nchunks], -1), ucol(uco[L.nchunks]),
-      usrc(uco[L.nchunks], -1);
-  for (int ch = 0; ch < L.nchunks; ch++)
-    for (int ln = 0; ln < 64; ln++) {
-      const int p = 64 * ch + ln, rl = rowL(p), ru = rowU(p);
-      for (int sl = 0; sl < lcl[ch]; sl++) lcol[size_t(lco[ch]) + 64 * sl + ln] = rl;
-      for (int sl = 0; sl < ucl[ch]; sl++) ucol[size_t(uco[ch]) + 64 * sl + ln] = ru;
-      if (p >= no) continue;
-      for (int side = 0; side < 2; side++) {  // 0: L at this position (row rl), 1: U (row ru)
-        const int row = side ? ru : rl, rch = row / 64, rln = row % 64;
-        const int len = int(L.rowmeta[row] & 63);
-        int kl = 0, ku = 1;
-        if (side) usrc[size_t(uco[ch]) + ln] = row << 6;  // slot 0: the diagonal block
-        for (int sl = 1; sl < len; sl++) {
-          const int j = L.colidx[size_t(L.chunk_off[rch]) + 64 * sl + rln];
-          if (j >= no || j == row || L.rowcolor[j] == L.rowcolor[row]) continue;
-          if (j < row) {
-            if (!side) {
-              lcol[size_t(lco[ch]) + 64 * kl + ln] = j;
-              lsrc[size_t(lco[ch]) + 64 * kl + ln] = row << 6 | sl;
-            }
-            kl++;
-          } else {
-            if (side) {
-              ucol[size_t(uco[ch]) + 64 * ku + ln] = j;
-              usrc[size_t(uco[ch]) + 64 * ku + ln] = row << 6 | sl;
-            }
-            ku++;
-          }
-        }
-      }
-    }
-  if ((rc = up(c->d_lperm, lperm, "lperm")) || (rc = up(c->d_uperm, uperm, "uperm")) ||
-      (rc = up(c->d_lpinv, lpinv, "lpinv")) || (rc = up(c->d_upinv, upinv, "upinv")) ||
-      (rc = up(c->d_llen, llen8, "llen")) || (rc = up(c->d_ulen, ulen8, "ulen")) ||
-      (rc = up(c->d_ldl, ldl, "ldl"))) {
+  if (int rc = c->create(mesh, params, degree, device, comm)) {
     g_err = c->err;
     return rc;
-  }
-  c->dl.lperm = c->d_lperm.p;
-  c->dl.uperm = c->d_uperm.p;
-  c->dl.lpinv = c->d_lpinv.p;
-  c->dl.upinv = c->d_upinv.p;
-  c->dl.llen = c->d_llen.p;
-  c->dl.ulen = c->d_ulen.p;
-  c->dl.ldl = c->d_ldl.p;
-  if ((rc = up(c->d_lchunk_len, lcl, "lchunk_len")) || (rc = up(c->d_lchunk_off, lco, "lchunk_off")) ||
-      (rc = up(c->d_lcolidx, lcol, "lcolidx")) || (rc = up(c->d_lsrc, lsrc, "lsrc")) ||
-      (rc = up(c->d_uchunk_len, ucl, "uchunk_len")) || (rc = up(c->d_uchunk_off, uco, "uchunk_off")) ||
-      (rc = up(c->d_ucolidx, ucol, "ucolidx")) || (rc = up(c->d_usrc, usrc, "usrc"))) {
-    g_err = c->err;
-    return rc;
-  }
-  {  // LDS-staged sweep lists (DevLayout lsx_* / usx_*): per colour, per 256-row block of the
-     // colour, the distinct rows its L / U split slots couple to; per split position its list
-     // position (0xFFFF for padding and the U diagonal slot)
-    const int nc = int(L.color_ptr.size()) - 1;
-    auto lists = [&](const std::vector<int> &cl, const std::vector<int> &co,
-                     const std::vector<int> &cc, int s0, auto rowat, std::vector<int> &ptr,
-                     std::vector<int> &lst, std::vector<uint16_t> &idx) -> bool {
-      idx.assign(cc.size(), 0xFFFF);
-      ptr.assign(1, 0);
-      lst.clear();
-      std::vector<int> cols;
-      for (int c = 0; c < nc; c++) {
-        const int a = L.color_ptr[c], b = L.color_ptr[c + 1];
-        for (int r0 = a; r0 < b; r0 += 256) {
-          const int r1 = std::min(b, r0 + 256);
-          cols.clear();
-          for (int p = r0; p < r1; p++) {  // positions; the row at p is rowat(p)
-            const int ch = p / 64, ln = p % 64, row = rowat(p);
-            for (int sl = s0; sl < cl[ch]; sl++) {
-              const int j = cc[size_t(co[ch]) + 64 * sl + ln];
-              if (j != row) cols.push_back(j);
-            }
-          }
-          std::sort(cols.begin(), cols.end());
-          cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-          if (cols.size() >= 0xFFFF) return false;
-          for (int p = r0; p < r1; p++) {
-            const int ch = p / 64, ln = p % 64, row = rowat(p);
-            for (int sl = s0; sl < cl[ch]; sl++) {
-              const size_t pos = size_t(co[ch]) + 64 * sl + ln;
-              if (cc[pos] != row)
-                idx[pos] = uint16_t(std::lower_bound(cols.begin(), cols.end(), cc[pos]) - cols.begin());
-            }
-          }
-          lst.insert(lst.end(), cols.begin(), cols.end());
-          ptr.push_back(int(lst.size()));
-        }
-      }
-      return true;
-    };
-    std::vector<int> lp, ll, up2, ul;
-    std::vector<uint16_t> li, ui;
-    const bool ok = lists(lcl, lco, lcol, 0, rowL, lp, ll, li) &&
-                    lists(ucl, uco, ucol, 1, rowU, up2, ul, ui);
-    int mx = 0;
-    for (size_t k = 0; ok && k + 1 < lp.size(); k++) mx = std::max(mx, lp[k + 1] - lp[k]);
-    for (size_t k = 0; ok && k + 1 < up2.size(); k++) mx = std::max(mx, up2[k + 1] - up2[k]);
-    if (ok && nc <= 256 && size_t(mx) * 3 * 8 <= 64 * 1024) {
-      if ((rc = up(c->d_lsx_ptr, lp, "lsx ptr")) || (rc = up(c->d_lsx_list, ll, "lsx list")) ||
-          (rc = up(c->d_lsx_idx, li, "lsx idx")) || (rc = up(c->d_usx_ptr, up2, "usx ptr")) ||
-          (rc = up(c->d_usx_list, ul, "usx list")) || (rc = up(c->d_usx_idx, ui, "usx idx"))) {
-        g_err = c->err;
-        return rc;
-      }
-      c->dl.lsx_ptr = c->d_lsx_ptr.p;
-      c->dl.lsx_list = c->d_lsx_list.p;
-      c->dl.lsx_idx = c->d_lsx_idx.p;
-      c->dl.usx_ptr = c->d_usx_ptr.p;
-      c->dl.usx_list = c->d_usx_list.p;
-      c->dl.usx_idx = c->d_usx_idx.p;
-      c->dl.sx_max = mx;
-      // host copies for the one-launch ILU(0) application's dependency lists (ilu_flow_build)
-      c->h_posrowL.resize(npos);
-      c->h_posrowU.resize(npos);
-      for (int pos = 0; pos < npos; pos++) {
-        c->h_posrowL[pos] = rowL(pos);
-        c->h_posrowU[pos] = rowU(pos);
-      }
-      c->h_lsx_ptr = lp;
-      c->h_lsx_list = ll;
-      c->h_usx_ptr = up2;
-      c->h_usx_list = ul;
-      c->ilu_flow[0].built = c->ilu_flow[1].built = false;
-    }
-  }
-  {  // row-contiguous block offsets and columns of the owned rows (fused ILU(0) factorisation)
-    std::vector<int> ro(L.n_owned + 1, 0), rcol;
-    rcol.reserve(size_t(L.nblocks));
-    for (int i = 0; i < L.n_owned; i++) {
-      const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
-      for (int sl = 0; sl < len; sl++)
-        rcol.push_back(L.colidx[size_t(L.chunk_off[ch]) + 64 * size_t(sl) + ln]);
-      ro[i + 1] = ro[i] + len;
-    }
-    if ((rc = up(c->d_rowoff, ro, "rowoff")) || (rc = up(c->d_rowcol, rcol, "rowcol"))) {
-      g_err = c->err;
-      return rc;
-    }
-  }
-  {  // spatial block order (DevLayout::blkmap) for the whole-matrix kernels (assembly, SpMV):
-     // each XCD takes one spatial slice of every colour, so the neighbour gathers of its rows
-     // share its L2.  With the gather-all assembly it pays 72.7 -> 58.8 us (the pipelined walk
-     // was latency-bound and did not see it; SpMV and sweeps neutral,
-     // profiles/r01/ab_blkmap_gather_all.log).  PNP_BLKMAP=0 turns it off (A/B)
-    const char *e = getenv("PNP_BLKMAP");
-    if (!(e && atoi(e) == 0) && L.n_owned > 0) {
-      int nblk = (L.n_owned + 255) / 256;
-      std::vector<double> key(nblk);
-      for (int b = 0; b < nblk; b++) {
-        int r = 256 * b, cc = L.rowcolor[r];
-        double lo = L.color_ptr[cc], hi = L.color_ptr[cc + 1];
-        key[b] = (r - lo) / std::max(1.0, hi - lo);
-      }
-      std::vector<int> order(nblk);
-      for (int b = 0; b < nblk; b++) order[b] = b;
-      std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return key[a] < key[b]; });
-      if ((rc = up(c->d_blkmap, order, "blkmap"))) {
-        g_err = c->err;
-        return rc;
-      }
-      c->dl.blkmap = c->d_blkmap.p;
-    }
-  }
-  {  // boundary segments for the ion-flux observable
-    const pnp::Mesh &mg = c->mesh;
-    auto ekey = [](int a, int b) {
-      if (a > b) std::swap(a, b);
-      return (long long)a << 32 | (unsigned)b;
-    };
-    std::unordered_map<long long, int> opp;
-    opp.reserve(size_t(mg.nb) * 2);
-    for (int b = 0; b < mg.nb; b++) opp[ekey(mg.bseg[2 * b], mg.bseg[2 * b + 1])] = -1;
-    for (int e = 0; e < mg.nt; e++)
-      for (int k = 0; k < 3; k++) {
-        auto it = opp.find(ekey(mg.tri[3 * e + k], mg.tri[3 * e + (k + 1) % 3]));
-        if (it != opp.end() && it->second < 0) it->second = mg.tri[3 * e + (k + 2) % 3];
-      }
-    std::vector<int4> segs;
-    for (int b = 0; b < mg.nb; b++) {
-      const int a = mg.bseg[2 * b], cc = mg.bseg[2 * b + 1], lo = L.g2l[std::min(a, cc)];
-      if (lo < 0 || lo >= L.n_owned) continue;  // another rank's segment
-      const int o = opp[ekey(a, cc)];
-      const int la = L.g2l[a], lc = L.g2l[cc], lop = o >= 0 ? L.g2l[o] : -1;
-      if (la < 0 || lc < 0 || lop < 0) {
-        g_err = "ion flux: the element of a boundary segment is not local";
-        return PNP_E_MESH;
-      }
-      segs.push_back(make_int4(la, lc, lop, mg.bgroup[b]));
-      c->fseg_group.push_back(mg.bgroup[b]);
-    }
-    if ((rc = up(c->d_fseg, segs, "flux segments"))) {
-      g_err = c->err;
-      return rc;
-    }
-  }
-  c->dl.lchunk_len = c->d_lchunk_len.p;
-  c->dl.lchunk_off = c->d_lchunk_off.p;
-  c->dl.lcolidx = c->d_lcolidx.p;
-  c->dl.uchunk_len = c->d_uchunk_len.p;
-  c->dl.uchunk_off = c->d_uchunk_off.p;
-  c->dl.ucolidx = c->d_ucolidx.p;
-  if ((rc = up(c->d_chunk_len, L.chunk_len, "chunk_len")) ||
-      (rc = up(c->d_chunk_off, L.chunk_off, "chunk_off")) ||
-      (rc = up(c->d_colidx, L.colidx, "colidx")) || (rc = up(c->d_rowmeta, L.rowmeta, "rowmeta")) ||
-      (rc = up(c->d_xy, xy, "xy")) || (rc = up(c->d_l2g, L.l2g, "l2g")) ||
-      (rc = up(c->d_send_idx, L.send_idx, "send_idx")) ||
-      (rc = up(c->d_color_idx, L.color_idx, "color_idx")) ||
-      (rc = up(c->d_rowcolor, L.rowcolor, "rowcolor"))) {
-    g_err = c->err;
-    return rc;
-  }
-  {
-    const char *e = getenv("PNP_XCD_REMAP");
-    c->dl.xcd_remap = (e && atoi(e) == 1) ? 1 : 0;  // measured: off for assembly / SpMV
-  }
-  c->dl.n_owned = L.n_owned;
-  c->dl.n_local = nloc;
-  c->dl.nchunks = L.nchunks;
-  c->dl.max_slots = L.chunk_len.empty() ? 0 : *std::max_element(L.chunk_len.begin(), L.chunk_len.end());
-  c->dl.ncolors = int(L.color_ptr.size()) - 1;
-  c->dl.chunk_len = c->d_chunk_len.p;
-  c->dl.chunk_off = c->d_chunk_off.p;
-  c->dl.colidx = c->d_colidx.p;
-  c->dl.rowmeta = c->d_rowmeta.p;
-  if (const char *ev = getenv("PNP_SPMV_LDS"); !(ev && atoi(ev) == 0)) {
-    // per 256-row block: its distinct columns, and per slot the column's position among them
-    const int nblk = (L.n_owned + 255) / 256;
-    std::vector<int> uptr(nblk + 1, 0), ulist;
-    std::vector<uint16_t> lidx(size_t(L.nslots), 0);
-    std::vector<int> cols, uown(nblk, 0);
-    int umax = 0, unmax = 0;
-    bool fits = true;
-    const bool own_last = [] {
-      const char *e = getenv("PNP_LIST_OWN_LAST");
-      return !(e && e[0] == '0');
-    }();
-    for (int b = 0; b < nblk && fits; b++) {
-      cols.clear();
-      const int r1 = std::min(L.n_owned, 256 * b + 256);
-      for (int i = 256 * b; i < r1; i++) {
-        const int ch = i / pnp::kRows, ln = i % pnp::kRows;
-        for (int sl = 0; sl < L.chunk_len[ch]; sl++)
-          cols.push_back(L.colidx[size_t(L.chunk_off[ch]) + 64 * size_t(sl) + ln]);
-      }
-      std::sort(cols.begin(), cols.end());
-      cols.erase(std::unique(cols.begin(), cols.end()), cols.end());
-      if (cols.size() > 65535) fits = false;
-      umax = std::max(umax, int(cols.size()));
-      // columns that are only a row's own slot 0 last (PNP_LIST_OWN_LAST, default): the assembly
-      // walk stages only the first uown[b] entries, the columns of slots >= 1 (fan neighbours; a
-      // block's rows are mostly of one colour, so its own rows are rarely among them); the SpMV
-      // stages all
-      std::vector<int> npos(cols.size());
-      int nn = 0;
-      if (own_last) {
-        std::vector<char> nb(cols.size(), 0);
-        for (int i = 256 * b; i < r1; i++) {
-          const int ch = i / pnp::kRows, ln = i % pnp::kRows;
-          for (int sl = 1; sl < L.chunk_len[ch]; sl++) {
-            const int j = L.colidx[size_t(L.chunk_off[ch]) + 64 * size_t(sl) + ln];
-            if (j != i) nb[std::lower_bound(cols.begin(), cols.end(), j) - cols.begin()] = 1;
-          }
-        }
-        for (size_t k = 0; k < cols.size(); k++)
-          if (nb[k]) npos[k] = nn++;
-        int no = nn;
-        for (size_t k = 0; k < cols.size(); k++)
-          if (!nb[k]) npos[k] = no++;
-      } else {
-        for (size_t k = 0; k < cols.size(); k++) npos[k] = int(k);
-        nn = int(cols.size());
-      }
-      uown[b] = nn;
-      unmax = std::max(unmax, nn);
-      for (int i = 256 * b; i < r1; i++) {
-        const int ch = i / pnp::kRows, ln = i % pnp::kRows;
-        for (int sl = 0; sl < L.chunk_len[ch]; sl++) {
-          const size_t pos = size_t(L.chunk_off[ch]) + 64 * size_t(sl) + ln;
-          lidx[pos] = uint16_t(npos[std::lower_bound(cols.begin(), cols.end(), L.colidx[pos]) - cols.begin()]);
-        }
-      }
-      std::vector<int> reord(cols.size());
-      for (size_t k = 0; k < cols.size(); k++) reord[npos[k]] = cols[k];
-      ulist.insert(ulist.end(), reord.begin(), reord.end());
-      uptr[b + 1] = int(ulist.size());
-    }
-    if (fits && size_t(umax) * 3 * 8 <= 64 * 1024) {
-      if ((rc = up(c->d_uptr, uptr, "uptr")) || (rc = up(c->d_ulist, ulist, "ulist")) ||
-          (rc = up(c->d_lidx, lidx, "lidx")) || (rc = up(c->d_uown, uown, "uown"))) {
-        g_err = c->err;
-        return rc;
-      }
-      c->dl.uptr = c->d_uptr.p;
-      c->dl.ulist = c->d_ulist.p;
-      c->dl.lidx = c->d_lidx.p;
-      c->dl.umax = umax;
-      c->dl.uown = c->d_uown.p;
-      c->dl.unmax = unmax;
-    }
-  }
-  c->dl.xy = c->d_xy.p;
-  c->dl.color_idx = c->d_color_idx.p;
-  c->dl.rowcolor = c->d_rowcolor.p;
-  // buffers
-  size_t nv3 = 3 * size_t(nloc);
-  auto al = [&](auto &buf, size_t n, const char *what) -> int {
-    hipError_t e2 = buf.alloc(n);  // zeroed, and the zeroing finished (DBuf::alloc)
-    if (e2 != hipSuccess) return cp->hipfail(e2, what);
-    return PNP_OK;
-  };
-  if ((rc = al(c->vals, size_t(L.nslots) * 8, "vals")) ||
-      (rc = al(c->lu, size_t(L.nslots) * 8, "lu")) ||
-      (rc = al(c->lvals, c->d_lsrc.n * 8, "lvals")) || (rc = al(c->uvals, c->d_usrc.n * 8, "uvals")) ||
-      (rc = al(c->tsgs, nv3, "sgs scratch")) || (rc = al(c->fluxx, nv3, "flux state")) ||
-      (rc = al(c->fluxout, 2 * c->fseg_group.size() + 2, "flux out")) ||
-      (rc = al(c->fluxred, 2 * 256, "flux reduce")) || (rc = al(c->x, nv3, "x")) ||
-      (rc = al(c->r, nv3, "r")) || (rc = al(c->rs, nv3, "rs")) || (rc = al(c->z, nv3, "z")) || (rc = al(c->rt, nv3, "rt")) ||
-      (rc = al(c->p, nv3, "p")) || (rc = al(c->v, nv3, "v")) || (rc = al(c->t, nv3, "t")) ||
-      (rc = al(c->y, nv3, "y")) || (rc = al(c->y2, nv3, "y2")) ||
-      (rc = al(c->ilu_y32buf, nv3, "ILU(0) intermediate")) || (rc = al(c->b, nv3, "b")) || (rc = al(c->prevu, nv3, "prevu")) ||
-      (rc = al(c->ext, 3 * size_t(c->mesh.nv), "ext")) ||
-      (rc = al(c->sendbuf, 3 * std::max<size_t>(1, L.send_idx.size()), "sendbuf")) ||
-      // up to 3 partials per workgroup (SpMV mode 4) / 2 (updates with <rt, s>)
-      (rc = al(c->partials,
-               3 * std::max<size_t>(size_t(pnp::blas_nparts(3LL * nloc)),
-                                    size_t(pnp::spmv_parts(L.n_owned))) + 64,
-               "partials")) ||
-      (rc = al(c->partials2,
-               2 * std::max<size_t>(size_t(pnp::blas_nparts(3LL * nloc)),
-                                    size_t(pnp::spmv_parts(L.n_owned))) + 64,
-               "partials2")) ||
-      (rc = al(c->S, 2, "scalars")) || (rc = al(c->redmw, pnp::kRedMwDoubles, "reduce ticket")) ||
-      (rc = al(c->dmask, 3 * size_t(L.n_owned), "dmask")) ||
-      (rc = al(c->rowflag, size_t(L.nchunks + 1) * pnp::kRows, "row flags")) ||
-      (rc = al(c->cvec, 3 * size_t(L.n_owned), "cvec")) || (rc = al(c->aux0, nloc, "aux0")) ||
-      (rc = al(c->aux1, nloc, "aux1"))) {
-    g_err = c->err;
-    return rc;
-  }
-  if ((e = hipHostMalloc(&c->hS, 3 * sizeof(pnp::Scalars))) != hipSuccess) {
-    g_err = std::string("hipHostMalloc: ") + hipGetErrorString(e);
-    return PNP_E_HIP;
-  }
-  if (c->dist) {  // halo-overlapped SpMV: interior / boundary 256-row blocks
-    const char *ev = getenv("PNP_HALO_OVERLAP");
-    if (!(ev && atoi(ev) == 0) && L.n_owned > 0) {
-      const int nblk = (L.n_owned + 255) / 256;
-      std::vector<int> order(nblk);
-      if (c->d_blkmap.p) {
-        CK(hipMemcpy(order.data(), c->d_blkmap.p, sizeof(int) * nblk, hipMemcpyDeviceToHost),
-           "blkmap");
-      } else {
-        for (int b = 0; b < nblk; b++) order[b] = b;
-      }
-      std::vector<int> bi, bb;
-      for (int b : order) {
-        bool bnd = false;
-        for (int i = 256 * b; i < std::min(L.n_owned, 256 * b + 256) && !bnd; i++) {
-          const int ch = i / pnp::kRows, ln = i % pnp::kRows, len = pnp::meta_len(L.rowmeta[i]);
-          for (int sl = 1; sl < len && !bnd; sl++)
-            bnd = L.colidx[size_t(L.chunk_off[ch]) + 64 * size_t(sl) + ln] >= L.n_owned;
-        }
-        (bnd ? bb : bi).push_back(b);
-      }
-      if ((rc = up(c->d_blk_int, bi, "interior blocks")) || (rc = up(c->d_blk_bnd, bb, "boundary blocks"))) {
-        g_err = c->err;
-        return rc;
-      }
-      c->n_blk_int = int(bi.size());
-      c->n_blk_bnd = int(bb.size());
-      c->split_spmv = true;
-      if (comm->rccl_unique_id) {
-        if ((e = hipStreamCreateWithFlags(&c->cstream, hipStreamNonBlocking)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&c->ev_ready, hipEventDisableTiming)) != hipSuccess ||
-            (e = hipEventCreateWithFlags(&c->ev_halo, hipEventDisableTiming)) != hipSuccess) {
-          g_err = std::string("halo stream: ") + hipGetErrorString(e);
-          return PNP_E_HIP;
-        }
-      }
-    }
-  }
-  if (degree > 1 && (rc = c->pk_build())) {
-    g_err = c->err;
-    return rc;
-  }
-  if (c->nranks > 1 && !comm->rccl_unique_id && !comm->local_group) {  // host-staged transport
-    if (!comm->host->exchange || !comm->host->allreduce_sum) {
-      g_err = "pnp_host_transport: exchange and allreduce_sum are required";
-      return PNP_E_ARG;
-    }
-    c->ht = *comm->host;
-    const size_t ns = 3 * std::max<size_t>(1, L.send_idx.size());
-    const size_t nr = 3 * std::max<size_t>(1, size_t(L.n_ghost));
-    if ((e = hipHostMalloc(&c->h_send, sizeof(double) * ns)) != hipSuccess ||
-        (e = hipHostMalloc(&c->h_recv, sizeof(double) * nr)) != hipSuccess) {
-      g_err = std::string("host transport staging: ") + hipGetErrorString(e);
-      return PNP_E_HIP;
-    }
-  }
-  if (c->nranks > 1 && !comm->rccl_unique_id && comm->local_group) {  // join the in-process group
-    std::shared_ptr<LocalGroup> g;
-    {
-      std::lock_guard<std::mutex> lk(g_groups_m);
-      auto &slot = g_groups[comm->local_group];
-      if (!slot || slot->size != c->nranks) {
-        slot = std::make_shared<LocalGroup>();
-        slot->size = c->nranks;
-        slot->members.assign(c->nranks, nullptr);
-        slot->host.assign(c->nranks, {});
-      }
-      g = slot;
-      if (g->members[c->rank]) {
-        g_err = "rank already present in local group";
-        return PNP_E_ARG;
-      }
-      g->members[c->rank] = c.get();
-    }
-    c->lg = g;
-    g->barrier();  // all ranks created before any collective
   }
   *out = c.release();
   return PNP_OK;
 }
+
 
 extern "C" void pnp_destroy(pnp_ctx *ctx) {
   if (!ctx) return;
@@ -2542,10 +2184,10 @@ extern "C" int pnp_get_info(pnp_ctx *c, pnp_info *info) {
   info->nat_flow_applies = c->nat_flow_n;
   info->nat_level_applies = c->nat_level_n;
   info->ilu_flow_applies = c->ilu_flow_n;
-  info->lslots_live = c->lslots_live;
-  info->uslots_live = c->uslots_live;
-  info->lsx_entries = (int64_t)c->h_lsx_list.size();
-  info->usx_entries = (int64_t)c->h_usx_list.size();
+  info->lslots_live = c->hl.lslots_live;
+  info->uslots_live = c->hl.uslots_live;
+  info->lsx_entries = (int64_t)c->hl.lsx_list.size();
+  info->usx_entries = (int64_t)c->hl.usx_list.size();
   info->pk_split_short = c->pkd.n_short;
   info->pk_split_long = c->pkd.n_long;
   info->pk_split_len = c->pkd.short_len;
@@ -3846,9 +3488,11 @@ extern "C" int pnp_timers_reset(pnp_ctx *c) {
 // host-only setup / inspection
 // ---------------------------------------------------------------------------------------------
 struct pnp_layout_buf {
+  pnp::Mesh mesh, tmesh;  // as pnp_ctx: for degree > 1 the node mesh and the triangle mesh
+  pnp::PkSpace pks;
   pnp::Fans fans;
   pnp::LocalLayout L;
-  std::vector<int> chunk_off32;
+  pnp::DerivedLayout D;  // filled by pnp_layout_derived
 };
 
 extern "C" int pnp_setup_boundary(const pnp_mesh *mesh, const pnp_params *params, int32_t nfields,
@@ -3895,25 +3539,96 @@ extern "C" int pnp_setup_initial_state(const pnp_mesh *mesh, const pnp_params *p
 
 extern "C" int pnp_layout_build(const pnp_mesh *mesh, int32_t rank, int32_t nranks,
                                 pnp_layout_buf **out) {
-  if (!out || nranks < 1 || rank < 0 || rank >= nranks) return PNP_E_ARG;
-  pnp::Mesh m;
-  std::string err;
-  if (!mesh_from_view(mesh, m, err)) {
-    g_err = err;
-    return PNP_E_MESH;
-  }
+  return pnp_layout_build_pk(mesh, 1, rank, nranks, out);
+}
+
+extern "C" int pnp_layout_build_pk(const pnp_mesh *mesh, int32_t degree, int32_t rank,
+                                   int32_t nranks, pnp_layout_buf **out) {
+  if (!out || degree < 1 || degree > 3 || nranks < 1 || rank < 0 || rank >= nranks)
+    return PNP_E_ARG;
   auto b = std::make_unique<pnp_layout_buf>();
-  if (!pnp::build_fans(m, b->fans, err)) {
-    g_err = err;
-    return PNP_E_MESH;
-  }
-  std::vector<int> part;
-  pnp::rcb_partition(m, nranks, part);
-  if (!pnp::build_local_layout(m, b->fans, part, rank, nranks, b->L, err)) {
+  std::string err;
+  if (!mesh_from_view(mesh, b->mesh, err) ||
+      !pnp::build_host_layout(b->mesh, degree, rank, nranks, b->tmesh, b->pks, b->fans, b->L, err)) {
     g_err = err;
     return PNP_E_MESH;
   }
   *out = b.release();
+  return PNP_OK;
+}
+
+extern "C" int pnp_layout_derived(pnp_layout_buf *b, const pnp_layout_knobs *knobs,
+                                  pnp_derived_layout *v) {
+  if (!b || !v) return PNP_E_ARG;
+  pnp::LayoutKnobs K = pnp::LayoutKnobs::from_env();
+  if (knobs) {
+    K.split_sort = knobs->split_sort != 0;
+    K.blkmap = knobs->blkmap != 0;
+    K.spmv_lds = knobs->spmv_lds != 0;
+    K.list_own_last = knobs->list_own_last != 0;
+    K.halo_overlap = knobs->halo_overlap != 0;
+    K.xcd_remap = knobs->xcd_remap;
+  }
+  std::string err;
+  if (!pnp::derive_layout(b->mesh, b->L, K, b->D, err)) {
+    g_err = err;
+    return PNP_E_MESH;
+  }
+  const pnp::DerivedLayout &D = b->D;
+  static_assert(sizeof(pnp::FluxSeg) == 4 * sizeof(int32_t), "flux segment record");
+  std::memset(v, 0, sizeof *v);
+  v->lslots = int64_t(D.split.lsrc.size());
+  v->uslots = int64_t(D.split.usrc.size());
+  v->lslots_live = D.split.lslots_live;
+  v->uslots_live = D.split.uslots_live;
+  v->lsx_entries = int64_t(D.sweep.llist.size());
+  v->usx_entries = int64_t(D.sweep.ulist.size());
+  v->lperm = D.split.lperm.data();
+  v->uperm = D.split.uperm.data();
+  v->lpinv = D.split.lpinv.data();
+  v->upinv = D.split.upinv.data();
+  v->llen = D.split.llen.data();
+  v->ulen = D.split.ulen.data();
+  v->ldl = D.split.ldl.data();
+  v->lchunk_len = D.split.lchunk_len.data();
+  v->lchunk_off = D.split.lchunk_off.data();
+  v->lcolidx = D.split.lcolidx.data();
+  v->lsrc = D.split.lsrc.data();
+  v->uchunk_len = D.split.uchunk_len.data();
+  v->uchunk_off = D.split.uchunk_off.data();
+  v->ucolidx = D.split.ucolidx.data();
+  v->usrc = D.split.usrc.data();
+  v->lsx_ptr = D.sweep.lptr.data();
+  v->lsx_list = D.sweep.llist.data();
+  v->usx_ptr = D.sweep.uptr.data();
+  v->usx_list = D.sweep.ulist.data();
+  v->lsx_idx = D.sweep.lidx.data();
+  v->usx_idx = D.sweep.uidx.data();
+  v->rowoff = D.rows.rowoff.data();
+  v->rowcol = D.rows.rowcol.data();
+  v->blkmap = D.blkmap.data();
+  v->fseg = D.flux.segs.empty() ? nullptr : &D.flux.segs[0].a;
+  v->fseg_group = D.flux.group.data();
+  v->uptr = D.spmv.uptr.data();
+  v->ulist = D.spmv.ulist.data();
+  v->uown = D.spmv.uown.data();
+  v->lidx = D.spmv.lidx.data();
+  v->blk_int = D.halo.interior.data();
+  v->blk_bnd = D.halo.boundary.data();
+  v->npos = 64 * b->L.nchunks;
+  v->sweep_usable = D.sweep.usable;
+  v->sx_max = D.sweep.sx_max;
+  v->n_sweep_blocks = D.sweep.usable ? int(D.sweep.lptr.size()) - 1 : 0;
+  v->nblk = (b->L.n_owned + 255) / 256;
+  v->n_blkmap = int(D.blkmap.size());
+  v->nfseg = int(D.flux.segs.size());
+  v->spmv_usable = D.spmv.usable;
+  v->umax = D.spmv.umax;
+  v->unmax = D.spmv.unmax;
+  v->halo_usable = D.halo.usable;
+  v->n_blk_int = int(D.halo.interior.size());
+  v->n_blk_bnd = int(D.halo.boundary.size());
+  v->xcd_remap = K.xcd_remap;
   return PNP_OK;
 }
 

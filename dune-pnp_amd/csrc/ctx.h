@@ -29,6 +29,7 @@
 #include "gmres_small.h"
 #include "idr_small.h"
 #include "kernels.h"
+#include "layout_derive.h"
 #include "mesh.h"
 #include "pk.h"
 
@@ -358,8 +359,9 @@ struct pnp_ctx {
     const char *e = std::getenv("PNP_ILU_FLOW");
     return (e && std::atoi(e) != 0) ? 1 : 0;
   }();
-  std::vector<int> h_posrowL, h_posrowU, h_lsx_ptr, h_lsx_list, h_usx_ptr, h_usx_list;
-  int64_t lslots_live = 0, uslots_live = 0;  // pnp_info
+  // what stays on the host of the derived layout (layout_derive.h): those copies, blkmap
+  // (pk_build) and the live-slot counts (pnp_info)
+  pnp::KeptLayout hl;
   struct IluFlowDev {
     bool built = false, ok = false;
     pnp::IluFlow F;
@@ -684,20 +686,38 @@ struct pnp_ctx {
   }
   hipError_t ssor_natural_levels_fixed();
   int set_fd(bool on);
+  // the steps of pnp_create_pk, in order (ctx.cc)
+  int create(const pnp_mesh *mesh_in, const pnp_params *pp, int degree_in, int device_in,
+             const pnp_comm *comm_in);
+  int create_host(const pnp_mesh *mesh_in, const pnp_params *pp, int degree_in,
+                  const pnp_comm *comm_in);
+  int create_device(int device_in, const pnp_comm *comm_in);
+  int upload_layout(const pnp::DerivedLayout &D, const pnp::LayoutKnobs &K);
+  int alloc_vectors();
+  int create_halo_stream(const pnp_comm *comm_in);
+  int create_host_transport(const pnp_comm *comm_in);
+  int join_local_group(const pnp_comm *comm_in);
   int pk_build();
   int fd_build();
   int ilu_factor();
   int split(int which);
 
-  // ---- aggregation AMG ------------------------------------------------------------------------
-  template <typename T>
-  int upv(DBuf<T> &d, const std::vector<T> &h, const char *what) {
-    hipError_t e = d.alloc(std::max<size_t>(1, h.size()));
+  // a host vector to a device buffer of (at least min_count) as many records.  upload leaves an
+  // empty vector's buffer null; upv gives it one zeroed element, for readers that take the pointer
+  template <typename T, typename U>
+  int upload(DBuf<T> &d, const std::vector<U> &h, const char *what, size_t min_count = 0) {
+    static_assert(sizeof(T) == sizeof(U), "upload: record size");
+    hipError_t e = d.alloc(std::max(min_count, h.size()));
     if (e == hipSuccess && !h.empty())
       e = hipMemcpy(d.p, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice);
     return e == hipSuccess ? PNP_OK : hipfail(e, what);
   }
+  template <typename T>
+  int upv(DBuf<T> &d, const std::vector<T> &h, const char *what) {
+    return upload(d, h, what, 1);
+  }
 
+  // ---- aggregation AMG ------------------------------------------------------------------------
   int amg_setup();
 
   // block-Jacobi sweeps on coarse level k + 1 (amg_d[k]): the configured count; PNP_AMG_DEEP_SWEEPS

@@ -20,6 +20,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import types
 from dataclasses import dataclass
 
 import numpy as np
@@ -293,6 +294,33 @@ class _Layout(C.Structure):
                 ("color_conflicts", C.c_int64)]
 
 
+class _LayoutKnobs(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("split_sort", "blkmap", "spmv_lds", "list_own_last",
+                                         "halo_overlap", "xcd_remap")]
+
+
+_DERIVED_U8 = ("lperm", "uperm", "lpinv", "upinv", "llen", "ulen", "ldl")
+_DERIVED_I32 = (("lchunk_len", "lchunk_off", "lcolidx", "lsrc", "uchunk_len", "uchunk_off",
+                 "ucolidx", "usrc"), ("lsx_ptr", "lsx_list", "usx_ptr", "usx_list"),
+                ("rowoff", "rowcol", "blkmap", "fseg", "fseg_group", "uptr", "ulist", "uown"),
+                ("blk_int", "blk_bnd"))
+_DERIVED_COUNTS = ("npos", "sweep_usable", "sx_max", "n_sweep_blocks", "nblk", "n_blkmap", "nfseg",
+                   "spmv_usable", "umax", "unmax", "halo_usable", "n_blk_int", "n_blk_bnd",
+                   "xcd_remap")
+
+
+class _DerivedLayout(C.Structure):  # pnp_derived_layout
+    _fields_ = ([(n, C.c_int64) for n in ("lslots", "uslots", "lslots_live", "uslots_live",
+                                          "lsx_entries", "usx_entries")] +
+                [(n, C.POINTER(C.c_uint8)) for n in _DERIVED_U8] +
+                [(n, C.POINTER(C.c_int32)) for n in _DERIVED_I32[0] + _DERIVED_I32[1]] +
+                [(n, C.POINTER(C.c_uint16)) for n in ("lsx_idx", "usx_idx")] +
+                [(n, C.POINTER(C.c_int32)) for n in _DERIVED_I32[2]] +
+                [("lidx", C.POINTER(C.c_uint16))] +
+                [(n, C.POINTER(C.c_int32)) for n in _DERIVED_I32[3]] +
+                [(n, C.c_int32) for n in _DERIVED_COUNTS])
+
+
 _LIB = None
 
 
@@ -491,12 +519,14 @@ def setup_initial_state(mesh: Mesh, params: Params, phi_pb):
 
 
 class Layout:
-    """The partition/local layout pnp_create builds (host-only, for inspection/tests)."""
+    """The partition/local layout pnp_create_pk builds (host-only, for inspection/tests)."""
 
-    def __init__(self, mesh: Mesh, rank=0, nranks=1):
+    def __init__(self, mesh: Mesh, rank=0, nranks=1, degree=1):
         buf = C.c_void_p()
         m = mesh.c()
-        _check(lib().pnp_layout_build(C.byref(m), int(rank), int(nranks), C.byref(buf)))
+        _check(lib().pnp_layout_build_pk(C.byref(m), int(degree), int(rank), int(nranks),
+                                         C.byref(buf)))
+        self._buf = buf
         v = _Layout()
         _check(lib().pnp_layout_view(buf, C.byref(v)))
 
@@ -522,7 +552,68 @@ class Layout:
         _check(lib().pnp_layout_regular_info(buf, C.byref(n), C.byref(r)))
         # pnp_asm_regular_info's counts: 64-row chunks, and those the assembly's regular walk takes
         self.regular_info = {"chunks": n.value, "regular_chunks": r.value}
-        lib().pnp_layout_free(buf)
+        self._derived = None
+
+    def __del__(self):
+        buf, self._buf = getattr(self, "_buf", None), None
+        if buf and _LIB is not None:  # (at interpreter exit the library may be gone first)
+            _LIB.pnp_layout_free(buf)
+
+    def derive(self, **knobs):
+        """The arrays a context derives from this layout and uploads (pnp_layout_derived), as numpy
+        copies in a namespace, with the counts.  knobs: split_sort, blkmap, spmv_lds, list_own_last,
+        halo_overlap, xcd_remap; the ones not given take their defaults.  No keyword at all: the
+        environment's, as a context reads them."""
+        k = None
+        if knobs:
+            k = _LayoutKnobs(1, 1, 1, 1, 1, 0)
+            for name, val in knobs.items():
+                if name not in dict(_LayoutKnobs._fields_):
+                    raise TypeError(f"unknown layout knob {name}")
+                setattr(k, name, int(val))
+        v = _DerivedLayout()
+        _check(lib().pnp_layout_derived(self._buf, C.byref(k) if k else None, C.byref(v)))
+
+        def arr(p, n, dt=np.int32):
+            return np.ctypeslib.as_array(p, (n,)).astype(dt).copy() if n else np.zeros(0, dt)
+        d = types.SimpleNamespace()
+        for name, _ in _DerivedLayout._fields_:
+            if not name.startswith("_") and isinstance(getattr(v, name), int):
+                setattr(d, name, getattr(v, name))
+        d.nchunks, d.ncolors = self.nchunks, self.ncolors
+        for name in _DERIVED_U8:
+            setattr(d, name, arr(getattr(v, name), v.npos, np.uint8))
+        for side, slots in (("l", v.lslots), ("u", v.uslots)):
+            setattr(d, side + "chunk_len", arr(getattr(v, side + "chunk_len"), self.nchunks))
+            setattr(d, side + "chunk_off", arr(getattr(v, side + "chunk_off"), self.nchunks + 1))
+            setattr(d, side + "colidx", arr(getattr(v, side + "colidx"), slots))
+            setattr(d, side + "src", arr(getattr(v, side + "src"), slots))
+            nb = v.n_sweep_blocks + 1 if v.sweep_usable else 0
+            setattr(d, side + "sx_ptr", arr(getattr(v, side + "sx_ptr"), nb))
+            setattr(d, side + "sx_list", arr(getattr(v, side + "sx_list"),
+                                             getattr(v, side + "sx_entries")))
+            setattr(d, side + "sx_idx", arr(getattr(v, side + "sx_idx"),
+                                            slots if v.sweep_usable else 0, np.uint16))
+        d.rowoff = arr(v.rowoff, self.n_owned + 1)
+        d.rowcol = arr(v.rowcol, int(d.rowoff[-1]))
+        d.blkmap = arr(v.blkmap, v.n_blkmap)
+        d.fseg = arr(v.fseg, 4 * v.nfseg).reshape(-1, 4)
+        d.fseg_group = arr(v.fseg_group, v.nfseg)
+        nb = v.nblk if v.spmv_usable else 0
+        d.uptr = arr(v.uptr, nb + 1 if v.spmv_usable else 0)
+        d.ulist = arr(v.ulist, int(d.uptr[-1]) if v.spmv_usable else 0)
+        d.uown = arr(v.uown, nb)
+        d.lidx = arr(v.lidx, self.nslots if v.spmv_usable else 0, np.uint16)
+        d.blk_int = arr(v.blk_int, v.n_blk_int)
+        d.blk_bnd = arr(v.blk_bnd, v.n_blk_bnd)
+        return d
+
+    @property
+    def derived(self):
+        """derive() with the environment's knobs, computed once"""
+        if self._derived is None:
+            self._derived = self.derive()
+        return self._derived
 
     def row_len(self, i):
         return int(self.rowmeta[i] & np.uint64(63))

@@ -807,7 +807,41 @@ typedef struct {
 } pnp_layout;
 /* the partition + local layout pnp_create would build for (rank, nranks) */
 int pnp_layout_build(const pnp_mesh *mesh, int32_t rank, int32_t nranks, pnp_layout_buf **out);
+/* the same for the P_k space pnp_create_pk would build (degree 1, 2 or 3); for degree > 1 the
+ * rows are the Lagrange nodes */
+int pnp_layout_build_pk(const pnp_mesh *mesh, int32_t degree, int32_t rank, int32_t nranks,
+                        pnp_layout_buf **out);
 int pnp_layout_view(const pnp_layout_buf *b, pnp_layout *view);
+/* The index arrays the context derives from the layout and uploads (DevLayout, dune-pnp_amd/csrc/
+ * layout_derive.h), read-only; they live in the buffer until the next pnp_layout_derived or
+ * pnp_layout_free.  knobs null: the environment's (PNP_SPLIT_SORT, PNP_BLKMAP, PNP_SPMV_LDS,
+ * PNP_LIST_OWN_LAST, PNP_HALO_OVERLAP, PNP_XCD_REMAP), as a context reads them */
+typedef struct {
+  int32_t split_sort, blkmap, spmv_lds, list_own_last, halo_overlap, xcd_remap;
+} pnp_layout_knobs;
+typedef struct {
+  int64_t lslots, uslots;            /* split slots incl. padding (pnp_info) */
+  int64_t lslots_live, uslots_live;  /* without padding; U counts the diagonal slot */
+  int64_t lsx_entries, usx_entries;  /* sweep list lengths (0: not usable) */
+  /* triangular split; position p = 64 chunk + lane holds row 64 chunk + lperm[p] / uperm[p] */
+  const uint8_t *lperm, *uperm, *lpinv, *upinv, *llen, *ulen, *ldl; /* npos each */
+  const int32_t *lchunk_len, *lchunk_off, *lcolidx, *lsrc;          /* nchunks, +1, lslots x 2 */
+  const int32_t *uchunk_len, *uchunk_off, *ucolidx, *usrc;
+  /* LDS sweep lists per 256-position block of a colour; idx 0xFFFF: padding / U diagonal */
+  const int32_t *lsx_ptr, *lsx_list, *usx_ptr, *usx_list; /* n_sweep_blocks + 1, *_entries */
+  const uint16_t *lsx_idx, *usx_idx;                      /* lslots, uslots */
+  const int32_t *rowoff, *rowcol;  /* n_owned + 1, rowoff[n_owned] */
+  const int32_t *blkmap;           /* n_blkmap: nblk, or 0 (identity) */
+  const int32_t *fseg;             /* nfseg x {a, c, opposite, group}, local vertices (P1) */
+  const int32_t *fseg_group;       /* nfseg */
+  /* LDS SpMV lists per 256-row block */
+  const int32_t *uptr, *ulist, *uown; /* nblk + 1, uptr[nblk], nblk */
+  const uint16_t *lidx;               /* nslots */
+  const int32_t *blk_int, *blk_bnd;   /* blocks without / with a ghost column, blkmap's order */
+  int32_t npos, sweep_usable, sx_max, n_sweep_blocks, nblk, n_blkmap, nfseg;
+  int32_t spmv_usable, umax, unmax, halo_usable, n_blk_int, n_blk_bnd, xcd_remap;
+} pnp_derived_layout;
+int pnp_layout_derived(pnp_layout_buf *b, const pnp_layout_knobs *knobs, pnp_derived_layout *view);
 /* pnp_asm_regular_info's counts for this layout (no context, no GPU) */
 int pnp_layout_regular_info(const pnp_layout_buf *b, int64_t *chunks, int64_t *regular_chunks);
 void pnp_layout_free(pnp_layout_buf *b);
