@@ -119,7 +119,8 @@ int pnp_ctx::halo_spmv(double *vin, double *yout, int mode, const double *w, con
                        int *nsp) {
   hipError_t e;
   if (mf_lin) mf_applies++;  // an interior + boundary pair counts once
-  if (!split_spmv) {
+  // the P_k element pass reads vin's ghosts in every element: halo, then both passes, unsplit
+  if (!split_spmv || (mf_lin && degree > 1)) {
     int rc = halo(vin, nf);
     if (rc) return rc;
     // the launch records the timer events itself (the kernel's own duration)
@@ -369,9 +370,10 @@ int pnp_ctx::assemble(const double *xdev, int jac) {
   if (kind < 0) return fail(PNP_E_STATE, "no operator set (pnp_set_operator)");
   int rc;
   if (jac && (rc = set_fd(fd_opt != 0))) return rc;
-  // matrix-free (P1, analytic): the Jacobian is the recorded point; only the residual the fused
-  // assembly would also have produced is computed now (Newton's right-hand side)
-  const bool mf = jac && mf_opt && degree == 1 && !fd_mode;
+  // matrix-free (analytic; P1: PNP_OPT_MATRIX_FREE, P_k: pnp_pk_matfree_set): the Jacobian is the
+  // recorded point; only the residual the fused assembly would also have produced is computed now
+  // (Newton's right-hand side)
+  const bool mf = jac && mf_on() && !fd_mode;
   if (mf && (rc = mf_record(xdev))) return rc;
   aa.x = xdev;
   aa.jac = (fd_mode || mf) ? 0 : jac;
@@ -450,12 +452,15 @@ int pnp_ctx::ensure_values() {
   fa.kconst = asm_kconst() ? 1 : 0;
   hipEvent_t t0 = tb(T_ASM);
   int piped = 0;
-  e = pnp::launch_assemble(dl, fa, stream, nullptr, nullptr, &piped);
+  if (degree > 1)
+    e = pnp::launch_pk_assemble(dl, fa, pkd, 1, stream);
+  else
+    e = pnp::launch_assemble(dl, fa, stream, nullptr, nullptr, &piped);
   if (e != hipSuccess) {
     vals_const_valid = false;
     return hipfail(e, "assemble at the linearisation point");
   }
-  asm_wrote(fa.kconst != 0, true);
+  asm_wrote(fa.kconst != 0, degree == 1);
   asm_piped += piped;
   te(T_ASM, t0);
   vals_stale = false;
@@ -474,7 +479,9 @@ int pnp_ctx::jacobi_prepare() {
     if (rc) return rc;
     e = mf_diag.alloc(std::max<size_t>(1, size_t(L.nchunks) * pnp::kRows * 6));
   }
-  if (e == hipSuccess) e = pnp::launch_jac_diag(dl, mf_aa, mf_diag.p, stream);
+  if (e == hipSuccess)
+    e = degree > 1 ? pnp::launch_pk_jac_diag(dl, mf_aa, pkd, mf_diag.p, stream)
+                   : pnp::launch_jac_diag(dl, mf_aa, mf_diag.p, stream);
   if (e != hipSuccess) return hipfail(e, "jacobi diagonal");
   mf_diag_valid = true;
   return PNP_OK;
@@ -2268,7 +2275,7 @@ int pnp_ctx::op_activate(int k, double dt, double z) {
   jacobian_drop();
   // a captured matrix-free application holds the operator's scalar arguments (dt, valency, ...) by
   // value, which the graph key does not see
-  if (mf_opt) graphs_clear();
+  if (mf_opt || pk_mf_opt) graphs_clear();
   // SELL padding slots point at the row itself and are never written by the assembly, so they
   // must hold zeros in the k-form layout of THIS operator (the SpMV multiplies them)
   vals_const_valid = false;
@@ -2677,8 +2684,8 @@ static int opt_seq_order(pnp_ctx *c, int old, int now) {
 static int opt_matrix_free(pnp_ctx *c, int, int now) {
   if (now && c->degree > 1)
     return c->fail(PNP_E_STATE,
-                   "PNP_OPT_MATRIX_FREE: P1 contexts only (the matrix-free application walks the "
-                   "P1 vertex fans; P_k contexts assemble)");
+                   "PNP_OPT_MATRIX_FREE: P1 contexts only (the option selects the P1 fan walk; a "
+                   "P_k context takes pnp_pk_matfree_set)");
   if (!now && c->mf_lin) {
     hipSetDevice(c->device);
     if (int rc = c->mf_settle()) return rc;
@@ -2776,6 +2783,30 @@ extern "C" int pnp_matfree_info(pnp_ctx *c, int64_t *applies, int64_t *value_ass
   if (!c) return PNP_E_ARG;
   if (applies) *applies = c->mf_applies;
   if (value_assemblies) *value_assemblies = c->value_assemblies;
+  return PNP_OK;
+}
+
+extern "C" int pnp_pk_matfree_set(pnp_ctx *c, int32_t on) {
+  if (!c) return PNP_E_ARG;
+  if (on != 0 && on != 1) return c->fail(PNP_E_ARG, "pnp_pk_matfree_set takes 0 or 1");
+  if (c->degree == 1)
+    return c->fail(PNP_E_STATE,
+                   "pnp_pk_matfree_set: P_k contexts of degree 2 or 3 only (a P1 context takes "
+                   "PNP_OPT_MATRIX_FREE)");
+  // as pnp_set_option: no graph captured in one form survives into the other, and none outlives an
+  // operator change made while the switch was off
+  c->graphs_clear();
+  if (!on && c->mf_lin) {
+    hipSetDevice(c->device);
+    if (int rc = c->mf_settle()) return rc;
+  }
+  c->pk_mf_opt = on;
+  return PNP_OK;
+}
+
+extern "C" int pnp_pk_matfree_get(pnp_ctx *c, int32_t *on) {
+  if (!c || !on) return PNP_E_ARG;
+  *on = c->degree > 1 ? c->pk_mf_opt : 0;
   return PNP_OK;
 }
 

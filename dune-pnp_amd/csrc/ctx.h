@@ -147,7 +147,8 @@ struct pnp_ctx {
   //   assembled       a Jacobian of the current operator is held.  Every reader of the flags down
   //                   to amg_valid sits behind it.  Set by jacobian_stored / seq_jacobian_stored,
   //                   cleared by jacobian_drop (and by md_run after a failed solve)
-  //   mf_lin          it is held as a linearisation point (PNP_OPT_MATRIX_FREE): jacobian_stored(mf)
+  //   mf_lin          it is held as a linearisation point (PNP_OPT_MATRIX_FREE, or on a P_k context
+  //                   pnp_pk_matfree_set): jacobian_stored(mf)
   //   vals_stale      ... and vals does not hold its values yet: jacobian_stored(mf) sets,
   //                   ensure_values clears; mf_settle and jacobian_drop clear both
   //   mf_diag_valid   mf_diag holds its diagonal blocks: jacobi_prepare sets, every transition clears
@@ -406,7 +407,12 @@ struct pnp_ctx {
   // the SELL values stale; halo_spmv and pnp_jacobian_apply compute J z from the point, and the
   // consumers of vals (SSOR / ILU(0) / AMG set-up, the CSR view, the export) first run the
   // ordinary assembly at the point (ensure_values).
-  int mf_opt = 0;
+  // P_k contexts (degree 2, 3) have a switch of their own, pnp_pk_matfree_set (pk_mf_opt; mf_opt
+  // stays 0 there, PNP_OPT_MATRIX_FREE = 1 being refused): the same record and flags, the two-pass
+  // kernels of pk_assemble.hip (launch_pk_jac_apply / launch_pk_jac_diag) in place of the fan walk,
+  // and halo_spmv unsplit (the element pass reads ghosts of the vector).
+  int mf_opt = 0, pk_mf_opt = 0;
+  bool mf_on() const { return degree == 1 ? mf_opt != 0 : pk_mf_opt != 0; }
   pnp::AsmArgs mf_aa{};
   DBuf<double> mf_x, mf_r;  // the point; the residual ensure_values' fused assembly also writes
   // Jacobi without SELL values: the diagonal blocks alone, one slot per chunk (launch_jac_diag),
@@ -629,6 +635,9 @@ struct pnp_ctx {
   hipError_t apply_op(const pnp::DevLayout &Lr, const double *vin, double *yout, int mode,
                       const double *w, double *parts, int *nparts, hipStream_t s,
                       const double *w2 = nullptr, hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr) {
+    if (mf_lin && degree > 1)
+      return pnp::launch_pk_jac_apply(Lr, mf_aa, pkd, vin, yout, mode, w, parts, nparts, s, w2, t0,
+                                      t1);
     if (mf_lin)
       return pnp::launch_jac_apply(Lr, mf_aa, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);
     return pnp::launch_spmv(Lr, nf, pat, vals.p, vin, yout, mode, w, parts, nparts, s, w2, t0, t1);

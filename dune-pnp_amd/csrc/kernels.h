@@ -701,7 +701,8 @@ struct PkDev {
   const int *enode = nullptr;
   const int *ioff = nullptr, *icnt = nullptr, *inc = nullptr;
   const uint32_t *islot = nullptr;
-  double *eres = nullptr;  // [nl][ne] element residual rows of the two-pass residual-only launch
+  double *eres = nullptr;  // [nl][ne] element residual rows of the two-pass residual-only launch;
+                           // between launches also the element rows of launch_pk_jac_apply
   double *ejac = nullptr;  // [ne][nl][W] element matrix + residual rows of the two-pass Jacobian
   // the two-pass Jacobian's gather split: 256-row blocks whose rows have at most short_len slots
   // (blk_short, in the blkmap order) and the others (blk_long); n_short 0: one launch
@@ -711,6 +712,19 @@ struct PkDev {
 hipError_t pk_upload_tables(int k, hipStream_t s);
 // jac 0 residual, 1 analytic Jacobian, 2 forward-difference Jacobian (PNP_JAC_FD)
 hipError_t launch_pk_assemble(const DevLayout &L, const AsmArgs &aa, const PkDev &P, int jac,
+                              hipStream_t s);
+// y = J(aa.x) v over owned rows without a stored matrix (pnp_pk_matfree_set): an element pass over
+// the P.ne local elements (it reads v's ghosts: halo first) into P.eres, then the row pass on the
+// rows of L.  aa: the linearisation point (x with ghosts, frozen potential, dt, z, mask); mode, w,
+// w2, partials, *nparts, t0 / t1 and the block subsets of L as launch_jac_apply
+hipError_t launch_pk_jac_apply(const DevLayout &L, const AsmArgs &aa, const PkDev &P,
+                               const double *v, double *y, int mode, const double *w,
+                               double *partials, int *nparts, hipStream_t s,
+                               const double *w2 = nullptr, hipEvent_t t0 = nullptr,
+                               hipEvent_t t1 = nullptr);
+// the diagonal of J(aa.x) alone, unmasked, row 64 c + l at dvals[64 c + l] (launch_jac_diag's
+// layout for a scalar operator)
+hipError_t launch_pk_jac_diag(const DevLayout &L, const AsmArgs &aa, const PkDev &P, double *dvals,
                               hipStream_t s);
 // cvec -= M(x_old): the DiffusionTOperator mass of the old time level
 hipError_t launch_pk_mass_apply(const DevLayout &L, const PkDev &P, const double *x_old,

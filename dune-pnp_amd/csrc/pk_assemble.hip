@@ -24,6 +24,8 @@
 
 #include <atomic>
 
+#include <hip/hip_ext.h>
+
 #include "kernels.h"
 #include "pk.h"
 
@@ -819,6 +821,224 @@ __global__ __launch_bounds__(kB) void k_pk_jac_gather(DevLayout L, PkDev D,
   r[row] = dmask[row] != 0 ? 0.0 : rv;
 }
 
+// ---- matrix-free Jacobian application (pnp_pk_matfree_set; DESIGN.md 4.9 "P_k") ----------------
+// y = J(x) v without a stored matrix, in the two passes of the residual-only launch.  Pass 1
+// (k_pk_elem_apply), one thread per local element: pk_jac_row's statements with sum_b J[a][b] v_b
+// taken inside the quadrature sum -- per point vq = sum v_i phi_i and gv = sum v_i grad phi_i, then
+// one pass over the NL test functions -- into eapp[a * ne + e] (the buffer and layout of eres: a
+// residual has finished its gather before this launch starts, and the other way round).  That is
+// O(NQ NL) per element where k_pk_elem_jac's matrices are O(NQ NL^2).  s: the one per-node field
+// the operator's Jacobian depends on -- the state x for PB, the frozen potential for the
+// diffusion operators, nothing (null, not loaded) for Poisson.
+constexpr int kBA = 128;  // threads per workgroup of the element pass
+template <int K>
+__global__ __launch_bounds__(kBA) void k_pk_elem_apply(PkDev D, const double *__restrict__ xy,
+                                                       const double *__restrict__ s,
+                                                       const double *__restrict__ v, PkArgs a) {
+  constexpr int NL = PkK<K>::NL;
+  const int ne = D.ne, e = blockIdx.x * kBA + threadIdx.x;
+  if (e >= ne) return;
+  int nd[NL];
+#pragma unroll
+  for (int i = 0; i < NL; i++) nd[i] = D.enode[size_t(i) * ne + e];
+  const double2 *xy2 = reinterpret_cast<const double2 *>(xy);
+  const PkGeo G = pk_geometry(xy2[nd[0]], xy2[nd[1]], xy2[nd[2]]);
+  double sl[NL], vl[NL], y[NL];
+#pragma unroll
+  for (int i = 0; i < NL; i++) {
+    sl[i] = s ? s[nd[i]] : 0.0;
+    vl[i] = v[nd[i]];
+    y[i] = 0.0;
+  }
+  const auto &T = tab<K>();
+  const double PI = a.pi;
+  if (a.kind == OP_DIFF_IE) {
+#pragma unroll 1
+    for (int q = 0; q < 7; q++) {
+      const auto &P = T.q5[q];
+      double vq = 0.0;
+#pragma unroll
+      for (int i = 0; i < NL; i++) vq += vl[i] * P.phi[i];
+      const double f = P.w * G.adet;
+#pragma unroll
+      for (int ra = 0; ra < NL; ra++) y[ra] += P.phi[ra] * vq * f;
+    }
+  }
+  if (a.kind == OP_PB || a.kind == OP_POISSON) {
+#pragma unroll 1
+    for (int q = 0; q < 4; q++) {
+      const auto &P = T.q3[q];
+      const double f = factor(G, P, a.cyl, PI);
+      double g[NL][2];
+      double u = 0.0, vq = 0.0, gv0 = 0.0, gv1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < NL; i++) {
+        grad(G, P, i, g[i][0], g[i][1]);
+        if (a.kind == OP_PB) u += sl[i] * P.phi[i];
+        vq += vl[i] * P.phi[i];
+        gv0 += vl[i] * g[i][0];
+        gv1 += vl[i] * g[i][1];
+      }
+      const double cv = a.kind == OP_PB ? 8 * PI * a.l_b * a.c0 * pb_cosh(u) * vq : 0.0;
+#pragma unroll
+      for (int ra = 0; ra < NL; ra++)
+        y[ra] += (g[ra][0] * gv0 + g[ra][1] * gv1 + cv * P.phi[ra]) * f;
+    }
+  } else {
+    const double sc = a.kind == OP_DIFF_IE ? a.dt : 1.0;
+#pragma unroll 1
+    for (int q = 0; q < 3; q++) {
+      const auto &P = T.q2[q];
+      double g[NL][2];
+      double vq = 0.0, gv0 = 0.0, gv1 = 0.0, gP0 = 0.0, gP1 = 0.0;
+#pragma unroll
+      for (int i = 0; i < NL; i++) {
+        grad(G, P, i, g[i][0], g[i][1]);
+        vq += vl[i] * P.phi[i];
+        gv0 += vl[i] * g[i][0];
+        gv1 += vl[i] * g[i][1];
+        gP0 += sl[i] * g[i][0];
+        gP1 += sl[i] * g[i][1];
+      }
+      const double f = P.w * G.adet, vz = vq * a.z;
+#pragma unroll
+      for (int ra = 0; ra < NL; ra++)
+        y[ra] += sc * ((g[ra][0] * gv0 + g[ra][1] * gv1 + vz * (gP0 * g[ra][0] + gP1 * g[ra][1])) * f);
+    }
+  }
+#pragma unroll
+  for (int ra = 0; ra < NL; ra++) D.eres[size_t(ra) * ne + e] = y[ra];
+}
+
+// Pass 2, one thread per owned row (row_block: the block map, the XCD remap and the block subsets
+// of launch_spmv): the row's incidences summed in ascending element order, in k_pk_res_gather's
+// batches of four; a constrained row gives y = v (columns are not eliminated, as in the stored
+// matrix).  mode, w, w2 and the partials as launch_spmv / launch_jac_apply: one group of kd
+// partials per workgroup, the xor tree inside each wave, then the four waves in order.
+__global__ __launch_bounds__(kB) void k_pk_apply_gather(DevLayout L, PkDev D,
+                                                        const uint8_t *__restrict__ dmask,
+                                                        const double *__restrict__ v,
+                                                        double *__restrict__ y, int mode,
+                                                        const double *__restrict__ w,
+                                                        const double *__restrict__ w2,
+                                                        double *__restrict__ partials) {
+  const int row = row_block(L, blockIdx.x, gridDim.x) * kB + threadIdx.x;
+  const bool live = row < L.n_owned;
+  double d[3] = {0, 0, 0};
+  if (live) {
+    const int chunk = row / kRows, lane = row % kRows;
+    const int cnt = D.icnt[row], ib = D.ioff[chunk] + lane;
+    const double *__restrict__ er = D.eres;
+    double R = 0.0;
+    for (int t0 = 0; t0 < cnt; t0 += 4) {
+      int code[4];
+      double c[4];
+#pragma unroll
+      for (int j = 0; j < 4; j++) code[j] = t0 + j < cnt ? D.inc[ib + (t0 + j) * kRows] : -1;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        c[j] = code[j] >= 0 ? er[size_t(code[j] & 15) * D.ne + (code[j] >> 4)] : 0.0;
+#pragma unroll
+      for (int j = 0; j < 4; j++)
+        if (code[j] >= 0) R += c[j];
+    }
+    if (dmask[row] != 0) R = v[row];
+    if (mode == 3) R = w[row] - R;  // residual form: y = w - J v
+    y[row] = R;
+    if (mode == 1 || mode == 2 || mode == 4) d[0] = R * w[row];
+    if (mode == 2 || mode == 4) d[1] = R * R;
+    if (mode == 4) d[2] = R * w2[row];
+  }
+  if (mode == 1 || mode == 2 || mode == 4) {
+    const int kd = mode == 4 ? 3 : mode;
+    __shared__ double sh[kB / 64][3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+      double t = d[k];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+      if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6][k] = t;
+    }
+    __syncthreads();
+    if (int(threadIdx.x) < kd) {
+      double t = 0;
+      for (int i = 0; i < kB / 64; i++) t += sh[i][threadIdx.x];
+      partials[size_t(kd) * blockIdx.x + threadIdx.x] = t;
+    }
+  }
+}
+
+// The diagonal of J(x) alone (Jacobi, Chebyshev): one thread per owned row walks its incidences
+// and sums each element's J[a][a] -- pk_jac_row's statements at b = a -- unmasked, into the
+// one-slot-per-chunk layout of launch_jac_diag (row 64 c + l at dvals[64 c + l]), which
+// launch_jacobi and the Chebyshev steps read through a layout whose chunk_off[c] = 64 c.
+template <int K>
+__global__ __launch_bounds__(kB) void k_pk_diag(DevLayout L, PkDev D, const double *__restrict__ s,
+                                                PkArgs a, double *__restrict__ dvals) {
+  constexpr int NL = PkK<K>::NL;
+  const int row = blockIdx.x * kB + threadIdx.x;
+  if (row >= L.n_owned) return;
+  const int chunk = row / kRows, lane = row % kRows;
+  const int ne = D.ne, cnt = D.icnt[row], ib = D.ioff[chunk] + lane;
+  const double2 *xy2 = reinterpret_cast<const double2 *>(L.xy);
+  const auto &T = tab<K>();
+  const double PI = a.pi;
+  double dsum = 0.0;
+  for (int t = 0; t < cnt; t++) {
+    const int code = D.inc[ib + t * kRows];
+    const int e = code >> 4, ra = code & 15;
+    int nd[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) nd[i] = D.enode[size_t(i) * ne + e];
+    const PkGeo G = pk_geometry(xy2[nd[0]], xy2[nd[1]], xy2[nd[2]]);
+    double sl[NL];
+#pragma unroll
+    for (int i = 0; i < NL; i++) sl[i] = s ? s[nd[i]] : 0.0;
+    double j = 0.0;
+    if (a.kind == OP_DIFF_IE) {
+      for (int q = 0; q < 7; q++) {
+        const auto &P = T.q5[q];
+        j += P.phi[ra] * P.phi[ra] * (P.w * G.adet);
+      }
+    }
+    if (a.kind == OP_PB || a.kind == OP_POISSON) {
+      for (int q = 0; q < 4; q++) {
+        const auto &P = T.q3[q];
+        const double f = factor(G, P, a.cyl, PI);
+        double c = 0.0;
+        if (a.kind == OP_PB) {
+          double u = 0.0;
+#pragma unroll
+          for (int i = 0; i < NL; i++) u += sl[i] * P.phi[i];
+          c = 8 * PI * a.l_b * a.c0 * pb_cosh(u) * P.phi[ra];
+        }
+        double ga0, ga1;
+        grad(G, P, ra, ga0, ga1);
+        j += (ga0 * ga0 + ga1 * ga1 + c * P.phi[ra]) * f;
+      }
+    } else {
+      const double sc = a.kind == OP_DIFF_IE ? a.dt : 1.0;
+      for (int q = 0; q < 3; q++) {
+        const auto &P = T.q2[q];
+        double gP0 = 0.0, gP1 = 0.0;
+#pragma unroll
+        for (int i = 0; i < NL; i++) {
+          double g0, g1;
+          grad(G, P, i, g0, g1);
+          gP0 += sl[i] * g0;
+          gP1 += sl[i] * g1;
+        }
+        double ga0, ga1;
+        grad(G, P, ra, ga0, ga1);
+        const double f = P.w * G.adet, drift = a.z * (gP0 * ga0 + gP1 * ga1);
+        j += sc * ((ga0 * ga0 + ga1 * ga1 + P.phi[ra] * drift) * f);
+      }
+    }
+    dsum += j;
+  }
+  dvals[size_t(chunk) * kRows + lane] = dsum;
+}
+
 // calcIonFlux (src/ionFlux.hh:50-91) on P_k: one thread per boundary segment of this rank;
 // seg = {element (local), local face, group}; the three fields at the face centre from the
 // element's nodes.  out[2s] / out[2s+1]: ip / im contributions (summed on the host in segment order)
@@ -1038,6 +1258,55 @@ hipError_t launch_pk_assemble(const DevLayout &L, const AsmArgs &aa, const PkDev
                                   aa.vals, s)
                   : row_launch<3>(L, P, aa.x, f0, f1, a, jac, 0, aa.cvec, aa.dmask, aa.r, nullptr,
                                   aa.vals, s);
+}
+
+// the per-node field the analytic Jacobian of aa's operator depends on (k_pk_elem_apply's s)
+static const double *pk_jac_field(const AsmArgs &aa) {
+  if (aa.kind == OP_PB) return aa.x;
+  if (aa.kind == OP_DIFF || aa.kind == OP_DIFF_IE) return aa.aux0;
+  return nullptr;
+}
+static bool pk_scalar_kind(int kind) {
+  return kind == OP_PB || kind == OP_POISSON || kind == OP_DIFF || kind == OP_DIFF_IE;
+}
+
+hipError_t launch_pk_jac_apply(const DevLayout &L, const AsmArgs &aa, const PkDev &P,
+                               const double *v, double *y, int mode, const double *w,
+                               double *partials, int *nparts, hipStream_t s, const double *w2,
+                               hipEvent_t t0, hipEvent_t t1) {
+  if (L.blkcount < 0) {  // an empty block subset
+    if (nparts) *nparts = 0;
+    return hipSuccess;
+  }
+  if ((P.k != 2 && P.k != 3) || !P.eres || !pk_scalar_kind(aa.kind) || mode < 0 || mode > 4)
+    return hipErrorInvalidValue;
+  const dim3 grid(L.blkcount > 0 ? L.blkcount : (L.n_owned + kB - 1) / kB), block(kB);
+  if (nparts) *nparts = int(grid.x);
+  if (L.n_owned == 0) return hipSuccess;
+  const PkArgs a{aa.kind, aa.cylindrical, 0, aa.l_b, aa.c0, aa.pi, aa.dt, aa.z};
+  const double *f = pk_jac_field(aa);
+  const dim3 ge((P.ne + kBA - 1) / kBA), be(kBA);
+  // t0 / t1: the start of the element pass and the end of the row pass
+  if (P.k == 2)
+    hipExtLaunchKernelGGL(k_pk_elem_apply<2>, ge, be, 0, s, t0, nullptr, 0, P, L.xy, f, v, a);
+  else
+    hipExtLaunchKernelGGL(k_pk_elem_apply<3>, ge, be, 0, s, t0, nullptr, 0, P, L.xy, f, v, a);
+  hipExtLaunchKernelGGL(k_pk_apply_gather, grid, block, 0, s, nullptr, t1, 0, L, P, aa.dmask, v, y,
+                        mode, w, w2, partials);
+  return hipGetLastError();
+}
+
+hipError_t launch_pk_jac_diag(const DevLayout &L, const AsmArgs &aa, const PkDev &P, double *dvals,
+                              hipStream_t s) {
+  if ((P.k != 2 && P.k != 3) || !pk_scalar_kind(aa.kind)) return hipErrorInvalidValue;
+  if (L.n_owned == 0) return hipSuccess;
+  const PkArgs a{aa.kind, aa.cylindrical, 0, aa.l_b, aa.c0, aa.pi, aa.dt, aa.z};
+  const dim3 grid((L.n_owned + kB - 1) / kB), block(kB);
+  if (P.k == 2)
+    hipLaunchKernelGGL(k_pk_diag<2>, grid, block, 0, s, L, P, pk_jac_field(aa), a, dvals);
+  else
+    hipLaunchKernelGGL(k_pk_diag<3>, grid, block, 0, s, L, P, pk_jac_field(aa), a, dvals);
+  return hipGetLastError();
 }
 
 hipError_t launch_pk_mass_apply(const DevLayout &L, const PkDev &P, const double *x_old,

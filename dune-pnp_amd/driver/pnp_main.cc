@@ -12,7 +12,8 @@
 //                 [--cheb-steps k]  (PNP_PREC_CHEBYSHEV, as --prec / --pb-prec / --amg-smoother cheb:
 //                                 block-Jacobi solves per application, 1 .. 16, default 3)
 //                 [--device d] [--out prefix]
-//                 [--matrix-free]  (PNP_OPT_MATRIX_FREE on every context: P1 only)
+//                 [--matrix-free]  (no matrix assembled: PNP_OPT_MATRIX_FREE on a P1 context,
+//                                 pnp_pk_matfree_set with --degree 2|3)
 //                 [--asm-full]  (PNP_OPT_ASM_REUSE_CONST = 0: every PnpOperator Jacobian assembly writes the
 //                                 state-independent planes too)
 //                 [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]  (the PNP phases'
@@ -70,7 +71,8 @@ static void usage() {
       "usage: pnp_main <config.cfg> [--refine k] [--mesh-scale s] [--mode stationary|instationary|md|pb]\n"
       "                [--steps n] [--prec none|ssor|ssor_natural|jacobi|ilu0|amg|cheb] [--pb-prec p]\n"
       "                [--cheb-steps k]\n"
-      "                [--device d] [--matrix-free] [--asm-full]\n"
+      "                [--device d] [--asm-full]\n"
+      "                [--matrix-free]  (no matrix assembled; every --degree)\n"
       "                [--method bicgstab|cg|gmres|fgmres|idr] [--restart m] [--idr-s s]\n"
       "                [--amg-smoother ssor|ilu0|jacobi|cheb]\n"
       "                [--out prefix] [--md-reduction r] [--md-loop host|device] [--md-reuse 0|1]\n"
@@ -321,7 +323,10 @@ int main(int argc, char **argv) {
     // program's own rounding order is unpinned)
     if (ref_order) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_SEQ_ORDER, 1), ctx.get());
     // operator applications computed from the linearisation state instead of the assembled matrix
-    if (matrix_free) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_MATRIX_FREE, 1), ctx.get());
+    if (matrix_free)
+      pnp_gpu::check(degree > 1 ? pnp_pk_matfree_set(ctx.get(), 1)
+                                : pnp_set_option(ctx.get(), PNP_OPT_MATRIX_FREE, 1),
+                     ctx.get());
     if (asm_full) pnp_gpu::check(pnp_set_option(ctx.get(), PNP_OPT_ASM_REUSE_CONST, 0), ctx.get());
     if (cheb_steps != 0) {
       const pnp_cheb_opts co{cheb_steps, 10.0, 20, 1.1, 0.0};

@@ -1004,6 +1004,17 @@ class Context:
         self._ck(lib().pnp_matfree_info(self.h, C.byref(a), C.byref(v)))
         return {"applies": a.value, "value_assemblies": v.value}
 
+    def pk_matfree(self, on):
+        """pnp_pk_matfree_set: matrix-free Jacobian application on a P_k context of degree 2 or 3
+        (what OPT_MATRIX_FREE is on a P1 context; E_STATE there).  Off assembles the values of the
+        current Jacobian if nobody had needed them yet."""
+        self._ck(lib().pnp_pk_matfree_set(self.h, C.c_int32(int(on))))
+
+    def pk_matfree_get(self):
+        v = C.c_int32()
+        self._ck(lib().pnp_pk_matfree_get(self.h, C.byref(v)))
+        return v.value
+
     def asm_info(self):
         """Jacobian assemblies since the context was created that wrote every plane of the SELL
         values, and PNP assemblies that kept the stored state-independent planes

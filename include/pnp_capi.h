@@ -535,8 +535,9 @@ enum {
    * PNP_PREC_JACOBI or PNP_PREC_CHEBYSHEV (which take the diagonal blocks from a walk of their
    * own), Newton included, never write the matrix (pnp_matfree_info counts).  Ignored, with the assembled path taken,
    * for forward-difference Jacobians (PNP_OPT_JAC_FD, PNP_JAC_FD) and in reference-order mode
-   * (PNP_OPT_SEQ_ORDER).  On a P_k context of degree > 1 setting 1 returns PNP_E_STATE.  Turning
-   * it off assembles the values of the current Jacobian if nobody had needed them yet.
+   * (PNP_OPT_SEQ_ORDER).  On a P_k context of degree > 1 setting 1 returns PNP_E_STATE and the
+   * option stays 0: such a context has the switch pnp_pk_matfree_set, with kernels of its own.
+   * Turning it off assembles the values of the current Jacobian if nobody had needed them yet.
    * 0 (default): the assembled SELL matrix and its SpMV, as before. */
   PNP_OPT_MATRIX_FREE = 12,
   /* 1 (default): the Jacobian assembly of PnpOperator (P1, analytic) writes the state-independent
@@ -581,12 +582,32 @@ int pnp_asm_regular_info(pnp_ctx *ctx, int64_t *chunks, int64_t *regular_chunks)
  * load, the others add +0.0.  P1 contexts only. */
 #define PNP_ROW_FLAG_LOAD 8
 int pnp_asm_row_flags(pnp_ctx *ctx, uint8_t *flags);
-/* PNP_OPT_MATRIX_FREE's counters, since the context was created.  applies: matrix-free operator
- * applications launched (the interior + boundary pair of a halo-overlapped application counts
- * once, as does an application captured into a replayed graph).  value_assemblies: assemblies
- * that wrote the SELL values, in either mode (with the option off: every Jacobian assembly).
- * Either pointer may be NULL. */
+/* The counters of PNP_OPT_MATRIX_FREE and of pnp_pk_matfree_set, since the context was created.
+ * applies: matrix-free operator applications launched (the interior + boundary pair of a
+ * halo-overlapped application counts once, as does an application captured into a replayed graph;
+ * on a P_k context the element pass and the row pass together count once).  value_assemblies:
+ * assemblies that wrote the SELL values, in either mode (with the switch off: every Jacobian
+ * assembly).  Either pointer may be NULL. */
 int pnp_matfree_info(pnp_ctx *ctx, int64_t *applies, int64_t *value_assemblies);
+/* Matrix-free Jacobian application on a P_k context of degree 2 or 3 (PB, Poisson, diffusion,
+ * diffusion + mass; the analytic Jacobian; DESIGN.md §4.9 "P_k").  on = 1: what
+ * PNP_OPT_MATRIX_FREE = 1 means on a P1 context -- a Jacobian assembly records the linearisation
+ * point and computes the residual, the SELL values are assembled at that point only when something
+ * reads them (SSOR, ILU(0), AMG, natural-order SSOR, the export, the CSR view), and solves with
+ * PNP_PREC_NONE, PNP_PREC_JACOBI or PNP_PREC_CHEBYSHEV never write the matrix -- with the P_k
+ * kernels of pk_assemble.hip: an element pass (per quadrature point v and grad v, then one pass
+ * over the element's test functions) and a row pass that sums each row's element entries in
+ * ascending element order, no atomics; the diagonal for Jacobi and Chebyshev from a row walk of
+ * its own.  With more than one rank the application is halo, element pass, row pass in that order
+ * (no interior / boundary overlap: the element pass reads the vector's ghosts).  Forward-difference
+ * Jacobians (PNP_OPT_JAC_FD, PNP_JAC_FD) take the assembled path and leave the switch alone.
+ * on = 0 (default): the assembled SELL matrix.  Degree 1: PNP_E_STATE (use PNP_OPT_MATRIX_FREE).
+ * The switch is a member of its own: pnp_get_option(PNP_OPT_MATRIX_FREE) reads 0 on a P_k context
+ * whatever it is set to, and pnp_set_option(PNP_OPT_MATRIX_FREE, 1) goes on returning PNP_E_STATE
+ * there.  Turning it off assembles the values of the current Jacobian if nobody had needed them
+ * yet.  Drops every captured graph.  pnp_matfree_info counts for both forms. */
+int pnp_pk_matfree_set(pnp_ctx *ctx, int32_t on);
+int pnp_pk_matfree_get(pnp_ctx *ctx, int32_t *on);
 /* PNP_METHOD_IDR's counter, since the context was created.  replacements: residual replacements
  * (the recurrence's norm met the test, the recomputed true norm did not, and the solve went on
  * from the true residual).  The pointer may be NULL. */
@@ -722,7 +743,9 @@ typedef struct {
  * A solve that breaks down or stops unconverged ends the run: res->status says which, the function
  * still returns PNP_OK, res->steps_done counts the completed steps and u is the state after the
  * last completed one.  P1 and P_k contexts, every transport, every method and preconditioner
- * pnp_linear_solve takes on scalar operators; PNP_OPT_MATRIX_FREE keeps its meaning.  Not in
+ * pnp_linear_solve takes on scalar operators; PNP_OPT_MATRIX_FREE (P1) and pnp_pk_matfree_set
+ * (P_k) keep their meaning: with PNP_PREC_NONE, PNP_PREC_JACOBI or PNP_PREC_CHEBYSHEV
+ * res->assemblies is then 0, and reuse = 1 keeps stage 1's linearisation point for stage 2.  Not in
  * reference-order mode (PNP_OPT_SEQ_ORDER: PNP_E_STATE).  PNP_E_ARG: nsteps < 0, dt <= 0, NULL
  * u / opts / res, cap > 0 with a NULL array.  After the call the context's operator is the Poisson
  * operator of the last solve. */
