@@ -3,7 +3,9 @@ pnp_ctx::amg_apply, the level-0 smoothers it is built from (the multicolour SSOR
 k_sgs_color, the multicolour ILU(0)), the aggregation of amg_setup.cc and the conditioning of what
 the cycle inverts.  No GPU; test infrastructure only.  tests/test_amg_ref_host.py holds the pieces
 to each other on the CPU, tests/test_gpu_amg.py and tests/test_gpu_amg_edges.py hold the kernels
-to them.
+to them.  The single applications of PNP_PREC_ILU0 (every PNP_OPT_ILU_F32 storage), PNP_PREC_SSOR
+and PNP_PREC_JACOBI restated here are held to themselves by tests/test_sweep_ref_host.py and the
+kernels to them by tests/test_gpu_sweep_edges.py.
 
 Orders.  External vectors are field-major over the global vertices, f * nv + g.  The kernels work
 in the layout's order: P.Layout rows 0 .. n_owned - 1 (colour-major), the fields of a row ascending;
@@ -22,6 +24,9 @@ MAX_LEVELS = 16
 PATS = {"pnp": [(f, g) for f in range(3) for g in range(3) if (f, g) not in ((1, 2), (2, 1))],
         "pnp_ie": [(f, g) for f in range(3) for g in range(3) if (f, g) != (2, 1)],
         "pb": [(0, 0)]}
+# the scalar operators (P1 names of tests/test_gpu_fan_walks.py, P_k names of tests/test_gpu_pk.py)
+PATS.update({k: [(0, 0)] for k in ("poisson", "diff", "diff+", "diff-", "diff_ie", "diff_ie+",
+                                   "diff_ie-")})
 
 
 def interleave(A, nv, nf):
@@ -161,39 +166,160 @@ def ilu0_dense(A, M):
     return A
 
 
-def ilu0_operator(J, lay, nf, pat):
-    """(apply, perm): apply(r) = (LU)^-1 r in the layout's order, L and U the ILU(0) factors of
-    the Jacobian on the stored block pattern `pat` (a list of (f, g)) without the same-colour
-    couplings; dense, so for at most about 1,000 unknowns, one rank"""
-    import scipy.linalg as sla
-    nv = J.shape[0] // nf
-    assert lay.n_owned == nv and lay.n_ghost == 0
+def ilu0_dense_recip(A, M):
+    """(F, dinv): the same factorisation in the kernels' form (k_ilu0_factor, k_ilu0_factor_fused):
+    a row's pivot is inverted once, when the row is finished, and the rows below multiply by the
+    stored reciprocal.  F's diagonal holds the pivots themselves, dinv their reciprocals.  Differs
+    from ilu0_dense by rounding only."""
+    A = A.copy()
+    n = A.shape[0]
+    dinv = np.zeros(n)
+    for i in range(n):
+        for k in np.nonzero(M[i, :i])[0]:
+            A[i, k] *= dinv[k]
+            q = np.nonzero(M[i, k + 1:] & M[k, k + 1:])[0] + k + 1
+            A[i, q] -= A[i, k] * A[k, q]
+        dinv[i] = 1.0 / A[i, i]
+    return A, dinv
+
+
+# The factors' storage roundings, from linalg.hip: the fused factorisation computes in fp64 and
+# writes every value of the split L / U storage -- the couplings, the diagonal block's lower and
+# upper entries and its inverted pivots -- once, as float(x) (PNP_OPT_ILU_F32 = 1) or as
+# to_bf16(float(x)) (= 2, 3); the sweeps convert back and compute in fp64.
+def round_f32(a):
+    """double -> float, round to nearest even (the kernels' float(x)), as float64"""
+    return np.asarray(a, dtype=np.float64).astype(np.float32).astype(np.float64)
+
+
+def round_bf16(a):
+    """linalg.hip to_bf16(float(x)): the double rounded to float, the float's upper 16 bits after
+    adding 0x7FFF and the lowest kept bit (round to nearest, ties to even), as float64"""
+    u = np.ascontiguousarray(np.asarray(a, dtype=np.float64).astype(np.float32)).view(np.uint32)
+    u = (u + np.uint32(0x7FFF) + ((u >> np.uint32(16)) & np.uint32(1))) & np.uint32(0xFFFF0000)
+    return u.view(np.float32).astype(np.float64)
+
+
+STORE_ROUND = {0: lambda a: np.asarray(a, dtype=np.float64), 1: round_f32, 2: round_bf16}
+
+
+def ilu0_mode(mode, nf):
+    """(storage, y32) of PNP_OPT_ILU_F32 = mode on a system of nf fields (ctx.h ilu_eff / ilu_fac /
+    ilu_y32): storage 0 fp64, 1 float, 2 bfloat16; y32: the forward intermediate in single
+    precision.  Scalar systems run modes 2 and 3 as mode 1."""
+    if nf == 1 and mode >= 2:
+        mode = 1
+    return (2, True) if mode == 3 else (mode, False)
+
+
+def ilu0_system(J, lay, nf, pat, drop=True):
+    """(Ap, M, perm): the rank's owned x owned block of J in the layout's order (dense; ghost
+    columns are outside the pattern, k_ilu0_factor's m >= L.n_owned) and the stored block pattern
+    `pat` (a list of (f, g)) on it as a mask -- drop: without the couplings of two different rows
+    of one colour, which the split storage has no slot for"""
+    nv, n = J.shape[0] // nf, lay.n_owned
     perm = local_perm(lay, nf, nv)
-    Ap = J.toarray()[np.ix_(perm, perm)]
+    Ap = J.tocsr()[perm][:, perm].toarray()
     M = np.zeros_like(Ap, dtype=bool)
-    colour = lay.rowcolor[:nv]
-    for r in range(nv):
+    colour = lay.rowcolor[:n]
+    same = []
+    for r in range(n):
         for c in lay.row_cols(r):
+            if c >= n:
+                continue
             for f, g in pat:
                 M[r * nf + f, c * nf + g] = True
-    assert not np.any(Ap[~M]), "Jacobian has entries outside the stored pattern"
-    for r in range(nv):
-        for c in lay.row_cols(r):
             if c != r and colour[c] == colour[r]:
-                M[r * nf:(r + 1) * nf, c * nf:(c + 1) * nf] = False
-    F = ilu0_dense(Ap, M)
-    lo, up = np.tril(F, -1) + np.eye(len(F)), np.triu(F)
+                same.append((r, c))
+    assert not np.any(Ap[~M]), "Jacobian has entries outside the stored pattern"
+    if drop:
+        for r, c in same:
+            M[r * nf:(r + 1) * nf, c * nf:(c + 1) * nf] = False
+    return Ap, M, perm
+
+
+def ilu0_factors(Ap, M, recip=False, store=0):
+    """(L, U, dinv): strictly lower and strictly upper factors (CSR) and the inverse pivots of the
+    ILU(0) of Ap on the pattern M, by ilu0_dense (recip False) or ilu0_dense_recip, each stored
+    value rounded once as the storage `store` does (STORE_ROUND)"""
+    return ilu0_stored(*ilu0_fp64(Ap, M, recip), store)
+
+
+def ilu0_fp64(Ap, M, recip=False):
+    """(L, U, dinv) in fp64, before any storage rounding: the factorisation is done once, however
+    many storages are then restated from it"""
+    if recip:
+        F, dinv = ilu0_dense_recip(Ap, M)
+    else:
+        F = ilu0_dense(Ap, M)
+        dinv = 1.0 / np.diag(F)
+    F = np.where(M, F, 0.0)  # a dropped coupling is in neither factor
+    return sp.csr_matrix(np.tril(F, -1)), sp.csr_matrix(np.triu(F, 1)), dinv
+
+
+def ilu0_stored(L, U, dinv, store):
+    """the fp64 factors as the storage `store` holds them: every value rounded once"""
+    rnd = STORE_ROUND[store]
+    return (sp.csr_matrix((rnd(L.data), L.indices, L.indptr), shape=L.shape),
+            sp.csr_matrix((rnd(U.data), U.indices, U.indptr), shape=U.shape), rnd(dinv))
+
+
+def ilu0_sweep(L, U, dinv, r, nf=1, y32=None):
+    """(LU)^-1 r as k_ilu0_solve does it: y = r - L y forward, x = (y - U x) dinv backward (the
+    pivots multiply), in fp64.  y32 (PNP_OPT_ILU_F32 = 3): a boolean per unknown, true where the
+    row's colour is not the last -- such a row's finished y is stored in single precision, and
+    the rows of other vertices and its own backward step read it from there; the fields of one
+    vertex are finished in registers first, so they read each other unrounded."""
+    n = len(r)
+    y, ys = np.zeros(n), np.zeros(n)
+    for i in range(n):
+        s, e = L.indptr[i], L.indptr[i + 1]
+        idx = L.indices[s:e]
+        src = y[idx] if y32 is None else np.where(idx // nf == i // nf, y[idx], ys[idx])
+        y[i] = r[i] - L.data[s:e] @ src
+        ys[i] = round_f32(y[i]) if y32 is not None and y32[i] else y[i]
+    x = np.zeros(n)
+    for i in range(n - 1, -1, -1):
+        s, e = U.indptr[i], U.indptr[i + 1]
+        x[i] = (ys[i] - U.data[s:e] @ x[U.indices[s:e]]) * dinv[i]
+    return x
+
+
+def ilu0_operator(J, lay, nf, pat, recip=False, mode=0, drop=True):
+    """(apply, perm): apply(r) = (LU)^-1 r in the layout's order, L and U the ILU(0) factors of
+    the rank's owned x owned block of the Jacobian on the stored block pattern `pat` without the
+    same-colour couplings (drop False: with them, which no kernel does).  mode: PNP_OPT_ILU_F32,
+    restated by ilu0_mode / ilu0_factors / ilu0_sweep; recip: the factorisation in the kernels'
+    form.  Dense, so for a few thousand unknowns."""
+    Ap, M, perm = ilu0_system(J, lay, nf, pat, drop)
+    store, y32 = ilu0_mode(mode, nf)
+    L, U, dinv = ilu0_factors(Ap, M, recip, store)
+    rows32 = None
+    if y32:
+        rows32 = np.repeat(lay.rowcolor[:lay.n_owned] != lay.ncolors - 1, nf)
 
     def apply(r):
-        return sla.solve_triangular(up, sla.solve_triangular(lo, r, lower=True), lower=False)
+        return ilu0_sweep(L, U, dinv, np.asarray(r, dtype=np.float64), nf, rows32)
     return apply, perm
 
 
-def ilu0_apply(J, lay, nf, pat, d):
-    """pnp_prec_apply(PNP_PREC_ILU0) with fp64 factors restated; external vectors"""
-    apply, perm = ilu0_operator(J, lay, nf, pat)
+def ilu0_apply(J, lay, nf, pat, d, **kw):
+    """pnp_prec_apply(PNP_PREC_ILU0) restated (fp64 factors unless mode says otherwise); external
+    vectors, zero outside the rank's owned unknowns"""
+    apply, perm = ilu0_operator(J, lay, nf, pat, **kw)
     v = np.zeros(J.shape[0])
     v[perm] = apply(np.asarray(d, dtype=np.float64)[perm])
+    return v
+
+
+def jacobi_apply(J, lay, nf, pat, d):
+    """pnp_prec_apply(PNP_PREC_JACOBI) restated from k_jacobi: every owned unknown divided by its
+    own diagonal entry (pointwise, not by the vertex block; a constrained row's is 1); external
+    vectors, zero outside the rank's owned unknowns"""
+    assert all((f, f) in pat for f in range(nf))
+    perm = local_perm(lay, nf, J.shape[0] // nf)
+    v = np.zeros(J.shape[0])
+    v[perm] = np.asarray(d, dtype=np.float64)[perm] / J.tocsr()[perm][:, perm].diagonal()
     return v
 
 

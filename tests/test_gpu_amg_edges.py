@@ -29,10 +29,11 @@ reference alone: N is the distance between two restated cycles whose rounded inv
 inv(A) and inv(A.T).T (two fp64 inverses that differ by rounding only), and the bound is
 max(1e-7, 8 N), the factor for rocSOLVER's pivot order against LAPACK's; never above 1e-5.
 
-P_k: the node layout (row order, colours) is not readable through the C ABI, so the aggregates are
-held to the exported Jacobian's graph (a partition; blocks = distinct pairs) instead of to the
-restated aggregation, and the SSOR cycle takes the context's own prec_apply(., PREC_SSOR) for the
-level-0 sweep, as the bf16 ILU(0) case takes a second context's sweep.
+P_k: the node layout (row order, colours) is read on the host as the P1 one is, P.Layout(mesh, rank,
+nranks, degree=k), so the SSOR cycle's level-0 sweep is amg_ref.multicolour_ssor on that layout
+(tests/test_gpu_sweep_edges.py holds the bare P_k sweep to the same restatement); the aggregates are
+held to the exported Jacobian's graph (a partition; blocks = distinct pairs), not to the restated
+aggregation.  Only the bf16 ILU(0) case takes a sweep from the library, a second context's.
 
 Measured on an MI355X (distance / max|v_ref|; N as above), part B and the large part A cases:
     case                   n      f32: N     distance   fp64: distance
@@ -283,7 +284,9 @@ def test_pk_cycle(mesh_id, k, opts, levels, smoother):
             assert info["levels"] >= 4 and info["rows"][-1] == 1
         cc, cb = R.conditioning(J, 1, aggs)
         assert cc <= COND_CAP and cb <= COND_CAP
-        smooth0 = None if smoother == "jacobi" else (lambda r: ctx.prec_apply(r, P.PREC_SSOR))
+        lay = P.Layout(mesh, degree=k)
+        assert lay.n_owned == S.nn and lay.max_slots == ctx.info()["max_slots"]
+        smooth0 = None if smoother == "jacobi" else (lambda r: R.multicolour_ssor(J, lay, 1, r))
         err, bound, N = cycle_figures(J, 1, aggs, d, v, opts.get("coarse_sweeps", 2), True, smooth0)
         print("AMG-FIG " + json.dumps(dict(id=f"{mesh_id}-P{k}-{smoother}", rows=info["rows"],
                                            err=err, bound=bound, N=N)))
